@@ -36,6 +36,10 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--warmup-ms", type=float, default=50.0,
+                    help="after the --warmup steps, more untimed steps until this much wall time has passed "
+                         "(an idle GPU takes a few ms of work to reach its clocks); the line reports the count "
+                         "as warmup_steps_run")
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS) + ["kkt"],
                     help="c1..c4: BASELINE.json configs (Riccati sweeps); kkt: the Newton-KKT step around "
                          "the sweep (SURVEY.md 8 row f1, NewtonKKTProblem(12, 4, 50), batch 4096)")
@@ -49,8 +53,13 @@ def parse_args():
                     help="multi-GPU: form of the exchange (sharding.GainsAllGather.mode); both: time each, "
                          "`value` is the better one and the line carries both")
     ap.add_argument("--blocks", type=int, default=5,
-                    help="timed blocks of --steps steps each; the line reports the MEDIAN block "
-                         "(ms_per_step, value) with min / max beside it")
+                    help="the --steps timed steps run back to back in one fenced region, whose wall time gives "
+                         "value and ms_per_step; ms_per_step_min / max are the per-step GPU times of this many "
+                         "consecutive blocks of that region (at most one per step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step (solution, "
+                         "gains, status; rank 0's shard for --gpus > 1) as DIR/<name>.npy, float32 or float64, "
+                         "at most 64 MB in all: a fixed seeded sample of the problems when the batch is larger")
     ap.add_argument("--layout", default="auto", choices=["auto", "full", "sym"],
                     help="layout of `mats` in HBM (include/sip_lqr_amd.h): full squares as LQR::Input holds them, or "
                          "Q and R as packed lower triangles (SIP_LQR_LAYOUT_SYMMETRIC); auto: sym where the shape has "
@@ -58,7 +67,71 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
                     help="target wall time of each cpu_baseline leg")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def block_sizes(steps, blocks):
+    """The `steps` timed steps split into min(blocks, steps) consecutive blocks of near-equal size."""
+    b = max(1, min(blocks, steps))
+    return [steps // b + (1 if i < steps % b else 0) for i in range(b)]
+
+
+def warm_up(step, warmup, warmup_ms, sync, agree=bool):
+    """Untimed steps before the timed ones: `warmup` of them, then chunks of more (doubling) until
+    `warmup_ms` of wall time has passed.  step() runs one step; sync() waits for the device; agree(flag)
+    makes every rank take the same decision.  Returns the number of steps run."""
+    t0 = time.perf_counter()
+    n, chunk = 0, warmup
+    while True:
+        for _ in range(chunk):
+            step()
+            n += 1
+        sync()
+        if not agree((time.perf_counter() - t0) * 1e3 < warmup_ms):
+            return n
+        chunk = max(1, n)
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs: at most this many bytes of .npy in all
+DUMP_SEED = 20240611     # fixes the sample of problems written when the batch does not fit
+
+
+def dump_sample(batch, row_bytes):
+    """Indices (sorted) of the problems --dump-outputs writes: every problem when the batch fits the
+    budget, else a fixed seeded sample; None for all."""
+    import numpy as np
+    rows = max(1, (DUMP_BYTES - 4096) // row_bytes)  # 4096: room for the .npy headers
+    if rows >= batch:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(batch, size=rows, replace=False))
+
+
+def take_outputs(arrays, float_dtype):
+    """Host copies of the rows dump_sample picks out of `arrays` (name -> [batch, ...] device tensors
+    sharing the batch dimension); floating arrays keep `float_dtype`, the rest become float64."""
+    import numpy as np
+    import torch
+    batch = next(iter(arrays.values())).shape[0]
+    esize = np.dtype(float_dtype).itemsize
+    row_bytes = sum((a[0].numel() if a.dim() > 1 else 1) * (esize if a.is_floating_point() else 8)
+                    for a in arrays.values())
+    idx = dump_sample(batch, row_bytes)
+    out = {}
+    for name, a in arrays.items():
+        if idx is not None:
+            a = a.index_select(0, torch.from_numpy(idx).to(a.device))
+        out[name] = a.cpu().numpy().astype(float_dtype if a.is_floating_point() else np.float64)
+    return out
+
+
+def write_outputs(dirname, host):
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def library_version():
@@ -189,25 +262,31 @@ def kkt_main(args):
     kkt = BatchedNewtonKKT(batch=batch, **dims)
     data = synthetic.make_newton_kkt_batch(kkt, seed=0, r2_max=1e2, **dims)
     sol = torch.zeros(batch, kkt.kkt_dim, dtype=torch.float64, device=kkt.device)
-    for _ in range(args.warmup):
-        kkt.factor_solve(*data, sol=sol)
+    warm_steps = warm_up(lambda: kkt.factor_solve(*data, sol=sol), args.warmup, args.warmup_ms, torch.cuda.synchronize)
+    # exactly `steps` timed steps back to back; an event after each of `blocks` consecutive blocks gives their
+    # per-step GPU times (min / max beside the wall-time figure)
+    sizes = block_sizes(args.steps, args.blocks)
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(len(sizes) + 1)]
     torch.cuda.synchronize()
-    block_s = []  # `blocks` timed blocks of exactly `steps` steps; the line reports the median block
-    for _ in range(max(1, args.blocks)):
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
+    t0 = time.perf_counter()
+    marks[0].record()
+    for b, nsteps in enumerate(sizes):
+        for _ in range(nsteps):
             kkt.factor_solve(*data, sol=sol)
-        torch.cuda.synchronize()
-        block_s.append(time.perf_counter() - t0)
-    elapsed = sorted(block_s)[len(block_s) // 2]
+        marks[b + 1].record()
+    torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+    block_s = [marks[b].elapsed_time(marks[b + 1]) * 1e-3 / nsteps for b, nsteps in enumerate(sizes)]
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, take_outputs({"sol": sol, "status": kkt.status}, np.float64))
     ms = elapsed / args.steps * 1e3
     alg_bytes = 8 * (kkt.model_len + 2 * kkt.z_dim + kkt.x_dim + kkt.y_dim + 2 * kkt.kkt_dim)
     achieved = batch * alg_bytes / (ms * 1e-3) / 1e9
     kkt_traffic, kkt_traffic_src = recorded_traffic(f"kkt:{kkt.kernel_name}") if batch == 4096 else (None, None)
     out = {
         "metric": "Newton-KKT factor+solves/sec", "value": batch * args.steps / elapsed, "unit": "solves/s",
-        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "blocks": max(1, args.blocks),
-        "ms_per_step_min": min(block_s) / args.steps * 1e3, "ms_per_step_max": max(block_s) / args.steps * 1e3,
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "warmup_steps_run": warm_steps, "ms_per_step": ms, "blocks": len(block_s),
+        "ms_per_step_min": min(block_s) * 1e3, "ms_per_step_max": max(block_s) * 1e3,
         "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         "config": {"workload": f"kkt: NewtonKKTProblem(n={n}, m={m}, T={T}), c={c}, g={g}, batch {batch}",
@@ -270,6 +349,7 @@ def main():
         return self_launch(args)
     if args.workload == "kkt":
         return kkt_main(args)
+    import numpy as np
     import torch
     import torch.distributed as dist
     from sip_optimal_control_amd import BatchedChainLQR, ChainShape, synthetic
@@ -312,7 +392,6 @@ def main():
     if sym:
         # the same problems with Q and R as packed lower triangles (the reference takes Q symmetric, lqr.cpp:658,
         # and reads the lower triangle of R only, lqr.cpp:697): 576 B less per problem-stage at (12, 4)
-        import numpy as np  # noqa: F401
         idx = torch.from_numpy(shape.packed().pack_index()).to(device)
         mats = full_mats[:, idx].contiguous()
         full_solver = BatchedChainLQR(n, m, T, batch, dtype=dtype, device=device)
@@ -330,10 +409,13 @@ def main():
         torch.cuda.synchronize(device)
 
     def run(ag, solver=solver, mats=mats):
-        """W warmup steps, then `blocks` timed blocks of exactly K steps, each between barrier +
-        synchronize fences; per block the max-over-ranks seconds.  Returns (list of block seconds,
-        mean kernel ms of this rank over all timed steps)."""
+        """The warm-up (warm_up: W steps, then more until --warmup-ms), then exactly K timed steps back to back between barrier + synchronize fences
+        (fences inside the region would idle the GPU between blocks and charge that to the steps).
+        Returns (max-over-ranks seconds per step, per-step GPU ms of each block of block_sizes on this
+        rank, mean kernel ms of this rank over all timed steps, host copies of what the last step
+        returned when --dump-outputs asks for them)."""
         events = []
+        last = {}
 
         def step(i, timed):
             # gains are double-buffered; with the gather on, buffer i%2 is only rewritten once every
@@ -343,7 +425,7 @@ def main():
                 e0 = torch.cuda.Event(enable_timing=True)
                 e1 = torch.cuda.Event(enable_timing=True)
                 e0.record(compute)
-            solver.factor_solve(mats, vecs, sol, out_gains)
+            last["sol"], last["gains"], last["status"] = solver.factor_solve(mats, vecs, sol, out_gains)
             if timed:
                 e1.record(compute)
                 events.append((e0, e1))
@@ -352,52 +434,71 @@ def main():
                 ag.launch(i)      # chunk exchanges on the side stream, overlapping sweep i+1
 
         it = 0
-        for _ in range(args.warmup):
+
+        def warm_step():
+            nonlocal it
             step(it, False)
+            it += 1
+
+        def agree(flag):  # every rank runs the same number of steps (collectives)
+            if world == 1:
+                return flag
+            t = torch.tensor([1.0 if flag else 0.0], device=device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            return bool(t.item())
+
+        warm_up(warm_step, args.warmup, args.warmup_ms, lambda: torch.cuda.synchronize(device), agree)
+        warm_steps = it
+        if ag:
+            ag.finish()
+        fence()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step(it, True)
             it += 1
         if ag:
             ag.finish()
-        block_s = []
-        for _ in range(max(1, args.blocks)):
-            fence()
-            t0 = time.perf_counter()
-            for _ in range(args.steps):
-                step(it, True)
-                it += 1
-            if ag:
-                ag.finish()
-            torch.cuda.synchronize(device)
-            local = time.perf_counter() - t0
-            fence()
-            el = torch.tensor([local], dtype=torch.float64, device=device)
-            if world > 1:
-                dist.all_reduce(el, op=dist.ReduceOp.MAX)
-            block_s.append(float(el.item()))
-        return block_s, sum(a.elapsed_time(b) for a, b in events) / max(1, len(events))
+        torch.cuda.synchronize(device)
+        local = time.perf_counter() - t0
+        fence()
+        el = torch.tensor([local / args.steps], dtype=torch.float64, device=device)
+        if world > 1:
+            dist.all_reduce(el, op=dist.ReduceOp.MAX)
+        block_ms, first = [], 0
+        for nsteps in block_sizes(args.steps, args.blocks):
+            block_ms.append(events[first][0].elapsed_time(events[first + nsteps - 1][1]) / nsteps)
+            first += nsteps
+        # taken before the next run() rewrites the shared sol / gains buffers
+        host = take_outputs(last, np.float64 if dt == "f64" else np.float32) if args.dump_outputs else None
+        return float(el.item()), block_ms, sum(a.elapsed_time(b) for a, b in events) / len(events), host, warm_steps
 
-    def summary(block_s, kernel_ms):
-        med = sorted(block_s)[len(block_s) // 2]
-        return {"value": world * batch * args.steps / med, "unit": "sweeps/s", "ms_per_step": med / args.steps * 1e3,
-                "ms_per_step_min": min(block_s) / args.steps * 1e3, "ms_per_step_max": max(block_s) / args.steps * 1e3,
-                "kernel_ms": kernel_ms}
+    dumps = {}
+
+    def summary(step_s, block_ms, kernel_ms, host, warm_steps, key):
+        dumps[key] = host
+        return {"value": world * batch / step_s, "unit": "sweeps/s", "ms_per_step": step_s * 1e3,
+                "ms_per_step_min": min(block_ms), "ms_per_step_max": max(block_ms), "kernel_ms": kernel_ms,
+                "warmup_steps_run": warm_steps}
 
     results = {}
     chunks = min(args.gather_chunks, batch)
     for mode in modes:
         ag = GainsAllGather(batch, shape.gains_len, dtype, device, chunks=chunks, mode=mode)
-        results[mode] = summary(*run(ag))
+        results[mode] = summary(*run(ag), mode)
         del ag
     if gather or not results:  # the same K steps without the exchange: independent shards, the compute-only bound
-        results["no_gather"] = summary(*run(None))
+        results["no_gather"] = summary(*run(None), "no_gather")
     full_layout = None
     if sym and world == 1:  # the same sweeps on the full squares, timed the same way, beside the headline
-        full_layout = summary(*run(None, full_solver, full_mats))
+        full_layout = summary(*run(None, full_solver, full_mats), "full_layout")
         full_layout["kernel"] = full_solver.kernel_name
     best = max(modes, key=lambda k: results[k]["value"]) if modes else "no_gather"
     head = results[best]
     elapsed, kernel_ms = head["ms_per_step"] * 1e-3 * args.steps, head["kernel_ms"]
 
     status_ok = bool((solver.status == 0).all().item())
+    if rank == 0 and args.dump_outputs:  # the headline path's last timed step
+        write_outputs(args.dump_outputs, dumps[best])
     if rank == 0:
         alg_bytes = shape.algorithmic_bytes(esize)
         achieved = alg_bytes * batch / (kernel_ms * 1e-3) / 1e9
@@ -409,10 +510,12 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "warmup_steps_run": head["warmup_steps_run"],
             "ms_per_step": elapsed / args.steps * 1e3,
-            # each of `blocks` blocks times exactly `steps` steps between fences; value / ms_per_step are
-            # the MEDIAN block's (box-to-box and launch-to-launch noise: VERDICT r02 weak #11)
-            "blocks": max(1, args.blocks), "ms_per_step_min": head["ms_per_step_min"],
+            # value / ms_per_step: wall time of the `steps` timed steps run back to back between fences;
+            # min / max: per-step GPU time of each of `blocks` consecutive blocks of them (box-to-box and
+            # launch-to-launch noise: VERDICT r02 weak #11)
+            "blocks": len(block_sizes(args.steps, args.blocks)), "ms_per_step_min": head["ms_per_step_min"],
             "ms_per_step_max": head["ms_per_step_max"],
             "higher_is_better": True,
             "scaling": "weak",

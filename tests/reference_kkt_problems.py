@@ -1,6 +1,6 @@
 """Model data of the reference's own Newton-KKT tests, as data.
 
-Re-expressed from /root/reference/tests/variable_dimensions_test.cpp
+Re-expressed from the reference's tests/variable_dimensions_test.cpp
 (`initialize_model` :71-133, `expect_kkt_solve` :135-181 and the dimension
 tables of the three theta_dim == 0 CallbackProvider tests :265-336) and the
 value distributions of benchmarks/newton_kkt_benchmark.cpp:58-262 (the

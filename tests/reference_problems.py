@@ -1,7 +1,7 @@
 """The hard-coded problems of the reference's own hot-path tests, as data.
 
 Re-expressed (not copied: these are the numeric fixtures, in numpy form) from
-/root/reference/tests/lqr_test.cpp.  Matrices are numpy (row, col) arrays; the
+the reference's tests/lqr_test.cpp.  Matrices are numpy (row, col) arrays; the
 Eigen comma initialisers of the reference fill row-major, which is what the
 nested lists below spell out.
 

@@ -1,5 +1,5 @@
 """Pins the CPU oracle against every known-answer / property test the reference
-holds for the hot path (/root/reference/tests/lqr_test.cpp).
+holds for the hot path (the reference's tests/lqr_test.cpp).
 
 The reference has no golden output vectors: its tests are status KATs, an
 integer topology KAT, KKT-residual bounds (< 1e-12) and agreement with a dense

@@ -1,5 +1,6 @@
 import os, sys, numpy as np, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, _ROOT); sys.path.insert(0, os.path.join(_ROOT, "tests"))
 from sip_optimal_control_amd import BatchedChainLQR, ChainShape, synthetic
 shapes = [tuple(int(v) for v in a.split(",")) for a in sys.argv[1:]] or [(10, 3), (6, 3), (12, 3)]
 for (n, m) in shapes:
