@@ -204,9 +204,12 @@ int sip_kkt_add_GTx_to_y(const sip_kkt_plan *plan, const double *d_model,
  * part of CallbackProvider::factor (:372-407) with its multi-right-hand-side
  * stagewise solve (:414-747), CallbackProvider::solve (:896-951) and the
  * theta terms of add_*x_to_y (:1023-1066, 1128-1158, 1221-1249, 1285-1308,
- * 1344-1367).  K^-1 J_theta runs as p launches of the plan's solve path, one
- * per column (the reference's multi-rhs block computes the same quantities
- * column by column, GEMM in place of GEMV).
+ * 1344-1367).  K^-1 J_theta runs its p columns through ONE multi-rhs
+ * Riccati solve (uniform chains: sip_lqr_solve_multi; trees and non-uniform
+ * chains: sip_lqr_tree_solve_multi, unless SIP_KKT_THETA_TREE_MULTI=0 is set
+ * when sip_kkt_plan_set_theta runs, which keeps one sip_kkt_solve per column);
+ * the reference's multi-rhs block computes the same quantities with GEMM in
+ * place of GEMV.
  *
  * theta arena [sip_kkt_theta_len(plan)] per problem (doubles, column-major
  * blocks, node i then edge i):

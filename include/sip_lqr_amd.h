@@ -332,6 +332,32 @@ int sip_lqr_tree_factor_solve_workspace(const sip_lqr_tree_plan *plan, const dou
                                         void *d_scratch, void *stream);
 const char *sip_lqr_tree_kernel_name(const sip_lqr_tree_plan *plan);
 
+/* Replaces: the multi-right-hand-side block of solve_stagewise_kkt_matrix (helpers.cpp:414-747, its LQR part
+ * :521-665: LQR::solve with GEMM in place of GEMV, reading LQR::Workspace directly; the caller is the theta Schur
+ * complement K^-1 J_theta, helpers.cpp:387) on any tree, for num_rhs >= 1 columns against ONE factorization.
+ *   right-hand sides: per problem and column sip_lqr_tree_rhs_len() doubles, node blocks q (n) | c (n), edge
+ *                     blocks r (m) at sip_lqr_tree_rhs_offset(kind 0 = node / 1 = edge, index) -- the output
+ *                     arena's layout; column c of problem b at (c * batch + b) * sip_lqr_tree_rhs_len();
+ *   outputs         : per problem and column the output arena (x | y per node, u per edge), column c of problem b
+ *                     at (c * batch + b) * sip_lqr_tree_output_len().
+ * Reads A, B and delta from d_input (its q, r, c are ignored) and the factor state from d_work (W, G_factor, K per
+ * edge; V, F_factor, sqrt_delta, sqrt_delta_inv per node), as sip_lqr_tree_factor() or
+ * sip_lqr_tree_factor_solve_workspace() leave it.  d_work is only read: the per-column v and k (and g, h) go to
+ * d_scratch, sip_lqr_tree_solve_multi_scratch_bytes(num_rhs) bytes of device scratch.  Instances whose
+ * d_status != SUCCESS are skipped and their output columns left untouched.  Trees that fit a size class of the
+ * fused kernels (state dimensions <= 15, control dimensions <= 8) carry up to 8 columns per wavefront through one
+ * backward / forward sweep (csrc/tree_mrhs_qw16.hpp), fetching every matrix operand of a step once; anything else
+ * (and plans created with SIP_LQR_TREE=general) runs the general engine column by column
+ * (sip_lqr_tree_multi_kernel_name() tells).  num_rhs < 1, a missing pointer or a latched invalid topology:
+ * SIP_LQR_ERR_INVALID_ARGUMENT before any HIP call.  Asynchronous on `stream`, kernels only. */
+size_t sip_lqr_tree_rhs_len(const sip_lqr_tree_plan *plan);
+size_t sip_lqr_tree_rhs_offset(const sip_lqr_tree_plan *plan, int kind, int index); /* (size_t)-1 if bad */
+size_t sip_lqr_tree_solve_multi_scratch_bytes(const sip_lqr_tree_plan *plan, int num_rhs);
+int sip_lqr_tree_solve_multi(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_work,
+                             const double *d_rhs_cols, double *d_out_cols, int num_rhs,
+                             const int32_t *d_status, void *d_scratch, void *stream);
+const char *sip_lqr_tree_multi_kernel_name(const sip_lqr_tree_plan *plan);
+
 /* Name of the kernel variant the plan dispatches to (static string). */
 const char *sip_lqr_kernel_name(const sip_lqr_plan *plan);
 

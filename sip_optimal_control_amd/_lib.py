@@ -68,6 +68,11 @@ _SIGNATURES = {
     "sip_lqr_tree_factor_solve": (ctypes.c_int, [_P] * 7),
     "sip_lqr_tree_factor_solve_workspace": (ctypes.c_int, [_P] * 7),
     "sip_lqr_tree_kernel_name": (ctypes.c_char_p, [_P]),
+    "sip_lqr_tree_rhs_len": (ctypes.c_size_t, [_P]),
+    "sip_lqr_tree_rhs_offset": (ctypes.c_size_t, [_P, ctypes.c_int, ctypes.c_int]),
+    "sip_lqr_tree_solve_multi_scratch_bytes": (ctypes.c_size_t, [_P, ctypes.c_int]),
+    "sip_lqr_tree_solve_multi": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
+    "sip_lqr_tree_multi_kernel_name": (ctypes.c_char_p, [_P]),
     "sip_lqr_kernel_name": (ctypes.c_char_p, [_P]),
     "sip_lqr_version": (ctypes.c_char_p, []),
     # include/sip_kkt_amd.h

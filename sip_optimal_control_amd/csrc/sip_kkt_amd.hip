@@ -62,6 +62,9 @@ struct sip_kkt_plan {
   // uniform chains: the fused theta passes of kkt_theta_chain_kernels.hpp (J_theta never assembled);
   // SIP_KKT_THETA_FUSED=0 keeps the generic passes
   bool chain_theta = false;
+  // tree plans: K^-1 J_theta through one sip_lqr_tree_solve_multi over all columns; SIP_KKT_THETA_TREE_MULTI=0
+  // keeps the column-by-column sip_kkt_solve loop
+  bool tree_theta_multi = false;
   sipamd::kkt::ChainTheta ct{};
   size_t lds_theta_rhs = 0, lds_theta_recover = 0, lds_theta_dot = 0;
   bool staged = false; // LDS-staged kernels (false: items too large for LDS, or SIP_KKT_VARIANT=direct)
@@ -266,6 +269,19 @@ hipError_t launch_condense(const sip_kkt_plan *p, const Regions &r, const double
 hipError_t launch_merge(const sip_kkt_plan *p, const Regions &r, int32_t *status, hipStream_t s) {
   hipLaunchKernelGGL(sipamd::kkt::merge_status_kernel, dim3((unsigned)((p->batch + 255) / 256)), dim3(256), 0, s,
                      r.reg, status, (long)p->batch, (int)SIP_KKT_NONPOSITIVE_REGULARIZATION);
+  return hipGetLastError();
+}
+
+// The generic right-hand-side kernels with the LQR offsets of `mt` (tree plans: p->meta, or a copy that places
+// q | c, r in the column layout of sip_lqr_tree_solve_multi).
+hipError_t launch_rhs_meta(const sip_kkt_plan *p, const Meta &mt, const Regions &r, const double *model,
+                           const double *b, const int32_t *status, hipStream_t s) {
+  if (p->staged)
+    hipLaunchKernelGGL(sipamd::kkt::rhs_staged_kernel, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_rhs, s,
+                       mt, model, b, r.inv, r.in1, status, (long)p->batch);
+  else
+    hipLaunchKernelGGL(sipamd::kkt::rhs_kernel, dim3(item_grid(p)), dim3(sipamd::kkt::TPB), 0, s, mt, model, b,
+                       r.inv, r.in1, status, (long)p->batch);
   return hipGetLastError();
 }
 
@@ -848,9 +864,13 @@ SIP_KKT_BLOCK_OP(GTx, AP_GT, 2, 0)
 namespace {
 
 struct ThetaRegions {
-  double *J, *KJ, *S, *rhs_sw, *sol_sw, *vecs_cols, *lsol_cols; // the last two: chain plans only
-  void *cws; // column workspace of sip_lqr_solve_multi (chain plans)
+  double *J, *KJ, *S, *rhs_sw, *sol_sw, *vecs_cols, *lsol_cols; // the last two: chain plans and tree multi-rhs plans
+  void *cws; // column workspace of sip_lqr_solve_multi (chain plans) / scratch of sip_lqr_tree_solve_multi (trees)
 };
+// doubles per problem and column of the right-hand-side / solution columns of the multi-rhs solve
+size_t theta_col_scalars(const sip_kkt_plan *p) {
+  return p->chain_kernels ? (size_t)p->in1_len : p->tree_theta_multi ? sip_lqr_tree_rhs_len(p->tree) : 0;
+}
 size_t theta_j_scalars(const sip_kkt_plan *p) { // per problem
   const size_t skkt = (size_t)p->x_dim + p->y_dim + p->z_dim, th = (size_t)p->theta_dim;
   return p->chain_theta ? (size_t)p->N * (th * th + th) : skkt * th;
@@ -866,7 +886,7 @@ ThetaRegions theta_regions(const sip_kkt_plan *p, void *theta_work) {
   r.S = (double *)(w + cur), cur = align256(cur + sizeof(double) * B * p->theta_dim * p->theta_dim);
   r.rhs_sw = (double *)(w + cur), cur = align256(cur + sizeof(double) * B * skkt);
   r.sol_sw = (double *)(w + cur), cur = align256(cur + sizeof(double) * B * skkt);
-  const size_t cols = p->chain_kernels ? sizeof(double) * B * (size_t)p->in1_len * p->theta_dim : 0;
+  const size_t cols = sizeof(double) * B * theta_col_scalars(p) * p->theta_dim;
   r.vecs_cols = (double *)(w + cur), cur = align256(cur + cols);
   r.lsol_cols = (double *)(w + cur), cur = align256(cur + cols);
   r.cws = w + cur;
@@ -948,6 +968,12 @@ int sip_kkt_plan_set_theta(sip_kkt_plan *p, int theta_dim) {
     if (p->chain_theta)
       p->name += " + fused theta passes";
   }
+  if (p->tree != nullptr) {
+    const char *tm = std::getenv("SIP_KKT_THETA_TREE_MULTI");
+    p->tree_theta_multi = !(tm != nullptr && tm[0] == '0');
+    if (p->tree_theta_multi)
+      p->name += " + tree multi-rhs";
+  }
   for (int b = 0; b < TH_NUM_BLOCKS; ++b)
     p->theta_meta.to[b] = (const long *)p->d_theta_longs + where[b];
   return SIP_LQR_OK;
@@ -966,8 +992,10 @@ size_t sip_kkt_theta_work_bytes(const sip_kkt_plan *p) {
   if (p == nullptr || p->theta_dim < 1)
     return 0;
   const size_t skkt = (size_t)p->x_dim + p->y_dim + p->z_dim, B = (size_t)p->batch, th = (size_t)p->theta_dim;
-  const size_t cols = p->chain_kernels ? align256(sizeof(double) * B * (size_t)p->in1_len * th) : 0;
-  const size_t cws = p->chain_kernels ? align256(sip_lqr_solve_multi_workspace_bytes(p->chain, p->theta_dim)) : 0;
+  const size_t cols = align256(sizeof(double) * B * theta_col_scalars(p) * th);
+  const size_t cws = p->chain_kernels      ? align256(sip_lqr_solve_multi_workspace_bytes(p->chain, p->theta_dim))
+                     : p->tree_theta_multi ? align256(sip_lqr_tree_solve_multi_scratch_bytes(p->tree, p->theta_dim))
+                                           : 0;
   return align256(sizeof(double) * B * theta_j_scalars(p)) + align256(sizeof(double) * B * skkt * th) +
          align256(sizeof(double) * B * th * th) + 2 * align256(sizeof(double) * B * skkt) + 2 * cols + cws;
 }
@@ -1081,6 +1109,32 @@ int sip_kkt_factor_theta(const sip_kkt_plan *p, const double *d_model, const dou
         });
     }
     if ((e = hipGetLastError()) != hipSuccess)
+      return report(e, "sip_kkt_factor_theta(recover)");
+  } else if (p->tree_theta_multi && p->input_status == SIP_KKT_SUCCESS) {
+    // K^-1 J_theta (helpers.cpp:387) on a tree: the right-hand sides of every column (the condense-rhs kernel once
+    // per column, writing q | c, r into the column layout of sip_lqr_tree_solve_multi instead of the LQR input
+    // arena), ONE multi-rhs Riccati solve over all columns against the factor state, then the multipliers of every
+    // column (the recover kernel once per column, reading x | y, u from the solution columns)
+    const Regions r = regions(p, d_work);
+    const long colJ = (long)p->batch * skkt, colV = (long)p->batch * (long)theta_col_scalars(p);
+    Meta cm = p->meta; // q, c, r at the x, y, u offsets of the output layout
+    cm.oq = cm.ox, cm.oc = cm.oy, cm.orr = cm.ou, cm.in1_len = cm.out_len;
+    Regions rc_ = r;
+    for (int col = 0; col < th && e == hipSuccess; ++col) {
+      rc_.in1 = t.vecs_cols + (size_t)col * colV;
+      e = launch_rhs_meta(p, cm, rc_, d_model, t.J + (size_t)col * colJ, d_status, s);
+    }
+    if (e != hipSuccess)
+      return report(e, "sip_kkt_factor_theta(rhs)");
+    rc = sip_lqr_tree_solve_multi(p->tree, r.in0, (const double *)r.lqr, t.vecs_cols, t.lsol_cols, th, d_status,
+                                  t.cws, s);
+    if (rc != SIP_LQR_OK)
+      return rc;
+    for (int col = 0; col < th && e == hipSuccess; ++col) {
+      rc_.out = t.lsol_cols + (size_t)col * colV;
+      e = launch_recover(p, rc_, d_model, t.J + (size_t)col * colJ, t.KJ + (size_t)col * colJ, d_status, s);
+    }
+    if (e != hipSuccess)
       return report(e, "sip_kkt_factor_theta(recover)");
   } else {
     for (int col = 0; col < th; ++col) { // K^-1 J_theta, one column per launch (helpers.cpp:387)

@@ -139,6 +139,7 @@ int sip_lqr_tree_plan_create(int64_t batch, int num_edges, int root,
       st.node = j, st.n = g.state_dims[j];
       st.oQ = g.oQ[j], st.oq = g.oq[j], st.oc = g.oc[j], st.od = g.od[j];
       st.oV = g.oV[j], st.oF = g.oF[j], st.osd = g.osd[j], st.osdi = g.osdi[j], st.ov = g.ov[j];
+      st.oxp = g.ox[j]; // (edge steps: the parent's, as edge_fields sets it; node steps: the node's own)
     };
     auto edge_fields = [&](sipamd::TreeStep &st, int e) {
       const int ch = g.children[e];
@@ -176,6 +177,9 @@ int sip_lqr_tree_plan_create(int64_t batch, int num_edges, int root,
         sipamd::TreeStep st{};
         node_fields(st, j);
         edge_fields(st, g.child_edges[ci]);
+        // the work-arena fields of a forward record are the CHILD's (the multi-rhs rollout solves with its F)
+        const int ch = st.child;
+        st.oV = g.oV[ch], st.oF = g.oF[ch], st.osd = g.osd[ch], st.osdi = g.osdi[ch], st.ov = g.ov[ch];
         st.flags = j == produced ? sipamd::TS_CHILD_LIVE : 0;
         steps.push_back(st);
         produced = st.child;
@@ -287,6 +291,70 @@ int sip_lqr_tree_solve(const sip_lqr_tree_plan *plan, const double *d_input,
   return SIP_LQR_OK;
 }
 
+
+size_t sip_lqr_tree_rhs_len(const sip_lqr_tree_plan *p) { return p ? (size_t)p->g.out_len : 0; }
+
+size_t sip_lqr_tree_rhs_offset(const sip_lqr_tree_plan *p, int kind, int index) {
+  // the output arena's layout: q | c where x | y are, r where u is
+  return sip_lqr_tree_offset(p, 2, kind, index);
+}
+
+namespace {
+// general engine: per problem the output layout (v at x, k at u) then g | h | f, reused by every column
+long general_cols_len(const sip_lqr_tree_plan *p) { return p->g.out_len + 2L * p->g.max_n + p->g.max_m; }
+} // namespace
+
+size_t sip_lqr_tree_solve_multi_scratch_bytes(const sip_lqr_tree_plan *p, int num_rhs) {
+  if (p == nullptr || num_rhs < 1 || p->topology_status != SIP_LQR_SUCCESS)
+    return 0;
+  const size_t B = (size_t)p->batch * sizeof(double);
+  if (p->fused != nullptr)
+    return B * (size_t)num_rhs * (size_t)p->fused->cols_len(p->sched);
+  return B * (size_t)general_cols_len(p);
+}
+
+int sip_lqr_tree_solve_multi(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_work,
+                             const double *d_rhs_cols, double *d_out_cols, int num_rhs, const int32_t *d_status,
+                             void *d_scratch, void *stream) {
+  if (plan == nullptr || num_rhs < 1 || d_status == nullptr || d_work == nullptr || d_scratch == nullptr ||
+      ((d_rhs_cols == nullptr || d_out_cols == nullptr) && plan->g.out_len > 0) ||
+      (d_input == nullptr && plan->g.in0_len > 0))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  if (plan->topology_status != SIP_LQR_SUCCESS)
+    return SIP_LQR_ERR_INVALID_ARGUMENT; // solve() needs a successful factor
+  sipamd::DeviceGuard on_device(plan->device);
+  if (on_device.err != hipSuccess)
+    return SIP_LQR_ERR_HIP;
+  hipStream_t s = (hipStream_t)stream;
+  const long batch = (long)plan->batch;
+  hipError_t e;
+  if (plan->fused != nullptr) { // all columns in one launch (tree_mrhs_qw16.hpp)
+    e = plan->fused->launch_multi(plan->sched, d_input, d_work, d_rhs_cols, d_out_cols, (double *)d_scratch, d_status,
+                                  batch, num_rhs, s);
+  } else { // the general engine, one launch per column, v / k / g | h | f in the scratch
+    sipamd::tree::Meta mt = plan->g.meta;
+    mt.oq = mt.ox, mt.oc = mt.oy, mt.orr = mt.ou, mt.in1_len = mt.out_len; // q | c, r: the output layout
+    const long col = batch * plan->g.out_len;
+    e = hipSuccess;
+    for (int k = 0; k < num_rhs && e == hipSuccess; ++k) {
+      hipLaunchKernelGGL((sipamd::tree::solve_cols_kernel<double>), dim3((unsigned)batch), dim3(sipamd::tree::TPB), 0, s,
+                         mt, d_input, d_rhs_cols + k * col, d_work, d_out_cols + k * col, (double *)d_scratch, mt.ox,
+                         mt.ou, plan->g.out_len, general_cols_len(plan), (const int *)d_status, batch);
+      e = hipGetLastError();
+    }
+  }
+  if (e != hipSuccess) {
+    std::fprintf(stderr, "sip_lqr_tree_solve_multi: %s\n", hipGetErrorString(e));
+    return SIP_LQR_ERR_HIP;
+  }
+  return SIP_LQR_OK;
+}
+
+const char *sip_lqr_tree_multi_kernel_name(const sip_lqr_tree_plan *plan) {
+  if (plan == nullptr)
+    return "";
+  return plan->fused != nullptr ? plan->fused->multi_name : "tree_generic/f64 column by column";
+}
 
 const char *sip_lqr_tree_kernel_name(const sip_lqr_tree_plan *plan) {
   if (plan == nullptr)

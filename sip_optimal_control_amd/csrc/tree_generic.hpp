@@ -270,29 +270,21 @@ __global__ __launch_bounds__(TPB) void factor_kernel(const Meta mt,
     status[b] = result;
 }
 
-// lqr.cpp:735-871, one problem per workgroup; needs a successful factor.
+// lqr.cpp:735-871 for one problem; needs a successful factor.  The factor state (W, G_factor, V,
+// F_factor, sqrt_delta, sqrt_delta_inv) is read from `ws`, K from `gain`; v goes to vbuf + ov[node],
+// k to kbuf + ok[edge], and g | h | f (max_n + max_m + max_n) to `g`.  solve_kernel passes the work /
+// gain arenas themselves; solve_cols_kernel a per-column scratch, so the work arena stays untouched.
 template <class S>
-__global__ __launch_bounds__(TPB) void solve_kernel(
-    const Meta mt, const S *in0_all, const S *in1_all, S *ws_all, S *gain_all,
-    S *out_all, const int *status, const long batch) {
-  const long b = blockIdx.x;
-  if (b >= batch || status[b] != 0)
-    return;
-  const int tid = threadIdx.x;
-  const S *in0 = in0_all + b * mt.in0_len;
-  const S *in1 = in1_all + b * mt.in1_len;
-  S *ws = ws_all + b * mt.ws_len;
-  S *gain = gain_all + b * mt.gain_len;
-  S *out = out_all + b * mt.out_len;
-  S *g = ws + mt.scratch_ws + (long)mt.max_m * mt.max_n +
-         (long)mt.max_n * mt.max_n;
+__device__ inline void solve_problem(const Meta &mt, const S *in0, const S *in1, const S *ws, const S *gain,
+                                     S *vbuf, const long *ov, S *kbuf, const long *ok, S *g, S *out,
+                                     const int tid) {
   S *h = g + mt.max_n, *f = h + mt.max_m;
 
   for (int order = 0; order < mt.num_nodes; ++order) { // :738-796
     const int node = mt.postorder[order];
     const int nn = mt.state_dims[node];
     const S *q = in1 + mt.oq[node];
-    S *v = ws + mt.ov[node];
+    S *v = vbuf + ov[node];
     for (int i = tid; i < nn; i += TPB)
       v[i] = q[i];
     wave_sync();
@@ -305,8 +297,8 @@ __global__ __launch_bounds__(TPB) void solve_kernel(
       const S *A = in0 + mt.oA[e], *B = in0 + mt.oB[e], *r = in1 + mt.orr[e];
       const S *cc = in1 + mt.oc[child], *dc = in0 + mt.od[child];
       const S *W = ws + mt.oW[e], *Gf = ws + mt.oG[e], *K = gain + mt.oK[e];
-      S *k = gain + mt.ok[e];
-      const S *vc = ws + mt.ov[child];
+      S *k = kbuf + ok[e];
+      const S *vc = vbuf + ov[child];
 
       for (int i = tid; i < nc; i += TPB)
         f[i] = dc[i] * vc[i] - cc[i];              // :778-779
@@ -348,7 +340,7 @@ __global__ __launch_bounds__(TPB) void solve_kernel(
     const S *cr = in1 + mt.oc[root], *dr = in0 + mt.od[root];
     const S *V = ws + mt.oV[root], *Ff = ws + mt.oF[root],
             *sd = ws + mt.osd[root], *sdi = ws + mt.osdi[root],
-            *v = ws + mt.ov[root];
+            *v = vbuf + ov[root];
     S *x = out + mt.ox[root], *y = out + mt.oy[root];
     for (int i = tid; i < n; i += TPB)
       f[i] = dr[i] * v[i] - cr[i];
@@ -378,10 +370,10 @@ __global__ __launch_bounds__(TPB) void solve_kernel(
       const int m = mt.control_dims[e];
       const S *A = in0 + mt.oA[e], *B = in0 + mt.oB[e];
       const S *cc = in1 + mt.oc[child], *dc = in0 + mt.od[child];
-      const S *K = gain + mt.oK[e], *k = gain + mt.ok[e];
+      const S *K = gain + mt.oK[e], *k = kbuf + ok[e];
       const S *Vc = ws + mt.oV[child], *Fc = ws + mt.oF[child],
               *sdc = ws + mt.osd[child], *sdic = ws + mt.osdi[child],
-              *vc = ws + mt.ov[child];
+              *vc = vbuf + ov[child];
       S *u = out + mt.ou[e];
       S *xc = out + mt.ox[child], *yc = out + mt.oy[child];
 
@@ -411,6 +403,38 @@ __global__ __launch_bounds__(TPB) void solve_kernel(
       wave_sync();
     }
   }
+}
+
+// lqr.cpp:735-871, one problem per workgroup; needs a successful factor.
+template <class S>
+__global__ __launch_bounds__(TPB) void solve_kernel(
+    const Meta mt, const S *in0_all, const S *in1_all, S *ws_all, S *gain_all,
+    S *out_all, const int *status, const long batch) {
+  const long b = blockIdx.x;
+  if (b >= batch || status[b] != 0)
+    return;
+  S *ws = ws_all + b * mt.ws_len;
+  S *gain = gain_all + b * mt.gain_len;
+  S *g = ws + mt.scratch_ws + (long)mt.max_m * mt.max_n + (long)mt.max_n * mt.max_n;
+  solve_problem<S>(mt, in0_all + b * mt.in0_len, in1_all + b * mt.in1_len, ws, gain, ws, mt.ov, gain, mt.ok, g,
+                   out_all + b * mt.out_len, (int)threadIdx.x);
+}
+
+// The same solve for one right-hand-side column (sip_lqr_tree_solve_multi on the general engine): mt's
+// in1 offsets (oq, oc, orr) and in1_len describe the column layout; the factor state is only read, and
+// v / k / g | h | f of a problem live in cols + b * col_len: v at ov[node], k at ok[edge], the rest at
+// col_vec.
+template <class S>
+__global__ __launch_bounds__(TPB) void solve_cols_kernel(
+    const Meta mt, const S *in0_all, const S *rhs_all, const S *ws_all, S *out_all, S *cols_all,
+    const long *ov, const long *ok, const long col_vec, const long col_len, const int *status, const long batch) {
+  const long b = blockIdx.x;
+  if (b >= batch || status[b] != 0)
+    return;
+  const S *ws = ws_all + b * mt.ws_len;
+  S *cols = cols_all + b * col_len;
+  solve_problem<S>(mt, in0_all + b * mt.in0_len, rhs_all + b * mt.in1_len, ws, ws, cols, ov, cols, ok,
+                   cols + col_vec, out_all + b * mt.out_len, (int)threadIdx.x);
 }
 
 } // namespace tree

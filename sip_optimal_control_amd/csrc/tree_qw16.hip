@@ -14,7 +14,25 @@ hipError_t launch(const TreeSchedule &ts, const double *input, double *output, d
                      input, output, work, pgains, spill, (int *)status, batch);
   return hipGetLastError();
 }
-#define TREE_CLASS(N, M) {N, M, "tree_factor_solve_qw16<" #N "," #M ">/f64", &launch<N, M, false>, &launch<N, M, true>}
+// columns per wavefront of the multi-rhs solve: 8 as in chain_mrhs.hpp; 4 from 12 states on, where a step's
+// operands (rows of W, A, V, K and both triangles of L, 5 N + 3 M doubles per lane) leave less room for columns
+template <int N, int M>
+constexpr int kMultiCols = N <= 10 ? 8 : 4;
+template <int N, int M>
+hipError_t launch_multi(const TreeSchedule &ts, const double *input, const double *work, const double *rhs_cols,
+                        double *out_cols, double *cols, const int32_t *status, long batch, int num_rhs, hipStream_t s) {
+  constexpr int P = kMultiCols<N, M>;
+  hipLaunchKernelGGL((tree_solve_mrhs_qw16<N, M, P>), dim3((unsigned)((batch + 3) / 4), (unsigned)((num_rhs + P - 1) / P)),
+                     dim3(64), 0, s, ts, input, work, rhs_cols, out_cols, cols, (const int *)status, batch, num_rhs);
+  return hipGetLastError();
+}
+template <int N, int M>
+long cols_len(const TreeSchedule &ts) {
+  return TreeColLayout<N, M>::len(ts);
+}
+#define TREE_CLASS(N, M)                                                                                            \
+  {N, M, "tree_factor_solve_qw16<" #N "," #M ">/f64", &launch<N, M, false>, &launch<N, M, true>,                    \
+   "tree_solve_mrhs_qw16<" #N "," #M ">/f64", &launch_multi<N, M>, &cols_len<N, M>}
 // sorted by cost: the first class that holds the largest node and the largest control wins
 // ((9, 3): the reference's variable-shape benchmark family at base dimension 8 -- states 7..9, controls 1..3,
 // benchmarks/lqr_benchmark.cpp:209-310 -- padded to (10, 4) before round 3)

@@ -43,7 +43,8 @@ namespace sipamd {
 // of every step.  Offsets are in doubles from the start of one problem inside its tree-native arena
 // (include/sip_lqr_amd.h).
 //   backward: for node in postorder { EDGE step per child edge, in CSR order; then the NODE step }
-//   forward : one step per edge, parents in preorder, child edges in CSR order
+//   forward : one step per edge, parents in preorder, child edges in CSR order; its work-arena fields
+//             oV, oF, osd, osdi, ov are those of the CHILD (read by the multi-rhs rollout, tree_mrhs_qw16.hpp)
 struct TreeStep {
   int kind;   // backward: 0 = edge, 1 = node
   int node;   // edge steps: the parent; node steps: the node
@@ -55,7 +56,7 @@ struct TreeStep {
   long oK, ok;                     // work arena: K, k of the edge
   long oW, oG;                     // work arena: W, G_factor of the edge (LQR::Workspace, lqr.hpp:109-135)
   long oV, oF, osd, osdi, ov;      // work arena: V, F_factor, sqrt_delta, sqrt_delta_inv, v of `node`
-  long ou, oxc, oyc, oxp;          // output arena: u of the edge, x / y of the child, x of the parent
+  long ou, oxc, oyc, oxp;          // output arena: u of the edge, x / y of the child, x of the parent (node steps: of `node`)
 };
 enum {
   TS_LOAD_V = 1,    // backward: [V | v] = [Q | q] of `node` first (first child edge of a node / a leaf's node step)

@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "tree_qw16.hpp"
+#include "tree_mrhs_qw16.hpp"
 
 namespace sipamd {
 
@@ -16,6 +17,13 @@ struct TreeClass {
   // the same sweep that also writes every LQR::Workspace field into the work arena (sip_lqr_tree_factor_solve_workspace)
   hipError_t (*launch_export)(const TreeSchedule &ts, const double *input, double *output, double *work, double *pgains,
                               double *spill, int32_t *status, long batch, hipStream_t s);
+  // several right-hand sides against the factor state of the work arena (tree_mrhs_qw16.hpp,
+  // sip_lqr_tree_solve_multi): `cols` per column and problem TreeColLayout<n, m>::len scalars
+  const char *multi_name;
+  hipError_t (*launch_multi)(const TreeSchedule &ts, const double *input, const double *work, const double *rhs_cols,
+                             double *out_cols, double *cols, const int32_t *status, long batch, int num_rhs,
+                             hipStream_t s);
+  long (*cols_len)(const TreeSchedule &ts);
 };
 
 // Smallest size class that holds a tree whose largest state / control dimensions are max_n / max_m;

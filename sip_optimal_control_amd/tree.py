@@ -121,8 +121,54 @@ class BatchedTreeLQR:
                                             ctypes.c_void_p(s.cuda_stream)), "sip_lqr_tree_solve")
         return self.output
 
-    def unpack_solution(self, b=0):
-        out = self.output[b].cpu().numpy()
+    @property
+    def multi_kernel_name(self):
+        return self._lib.sip_lqr_tree_multi_kernel_name(self._plan).decode()
+
+    @property
+    def rhs_len(self):
+        return self._lib.sip_lqr_tree_rhs_len(self._plan)
+
+    def pack_rhs(self, columns):
+        """columns: list (num_rhs) of lists (batch) of dicts with per-node "q", "c" and per-edge "r" (the keys
+        pack() takes) -> device tensor (num_rhs, batch, rhs_len) in the layout of sip_lqr_tree_solve_multi."""
+        L = self.rhs_len
+        host = np.zeros((len(columns), self.batch, max(1, L)))
+        for col, problems in enumerate(columns):
+            for b, blocks in enumerate(problems):
+                for node, n in enumerate(self.state_dims):
+                    o = self._lib.sip_lqr_tree_rhs_offset(self._plan, 0, node)
+                    host[col, b, o:o + n] = np.asarray(blocks["q"][node], dtype=np.float64).reshape(-1)
+                    host[col, b, o + n:o + 2 * n] = np.asarray(blocks["c"][node], dtype=np.float64).reshape(-1)
+                for e, m in enumerate(self.control_dims):
+                    o = self._lib.sip_lqr_tree_rhs_offset(self._plan, 1, e)
+                    host[col, b, o:o + m] = np.asarray(blocks["r"][e], dtype=np.float64).reshape(-1)
+        return torch.from_numpy(host).to(self.device)
+
+    def solve_multi(self, rhs_cols, out_cols=None):
+        """LQR::solve for several right-hand sides against the factor state in `work` (left by factor() or
+        factor_solve(workspace=True)); rhs_cols: (num_rhs, batch, rhs_len) float64 on the device (pack_rhs).
+        Returns the output columns (num_rhs, batch, output_len); problems whose status != 0 keep what
+        out_cols held."""
+        rhs_cols = rhs_cols.contiguous()
+        num_rhs = rhs_cols.shape[0]
+        if out_cols is None:
+            out_cols = torch.zeros(num_rhs, self.batch, max(1, self.out_len), dtype=torch.float64, device=self.device)
+        need = self._lib.sip_lqr_tree_solve_multi_scratch_bytes(self._plan, num_rhs)
+        if getattr(self, "_multi_scratch", None) is None or self._multi_scratch.numel() < need:
+            self._multi_scratch = torch.empty(max(1, need), dtype=torch.uint8, device=self.device)
+        s = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_tree_solve_multi(self._plan, ctypes.c_void_p(self.input.data_ptr()),
+                                                  ctypes.c_void_p(self.work.data_ptr()),
+                                                  ctypes.c_void_p(rhs_cols.data_ptr()),
+                                                  ctypes.c_void_p(out_cols.data_ptr()), num_rhs,
+                                                  ctypes.c_void_p(self.status.data_ptr()),
+                                                  ctypes.c_void_p(self._multi_scratch.data_ptr()),
+                                                  ctypes.c_void_p(s.cuda_stream)), "sip_lqr_tree_solve_multi")
+        return out_cols
+
+    def unpack_solution(self, b=0, output=None):
+        out = (self.output[b] if output is None else output[b]).cpu().numpy()
         x, y, u = [], [], []
         for node, n in enumerate(self.state_dims):
             o = self.offset(2, 0, node)
