@@ -617,3 +617,153 @@ int lqr_oracle_chain_batch(int n, int m, int T, long batch, const double *mats,
   }
   return 0;
 }
+
+/* ---- packed tree batch (test convenience) ------------------------------- */
+
+/* Per-node and per-edge offsets (in scalars) into one problem of the packed
+ * tree layout of lqr_oracle.h; the five tables have N, E, N, E and E
+ * entries.  Returns the problem's nodes|edges|sol|gains lengths in lens[4]. */
+static void tree_layout(int E, const int *parents, const int *children,
+                        const int *sd, const int *cd, long *node_off,
+                        long *edge_off, long *sol_node_off, long *sol_edge_off,
+                        long *gains_off, long lens[4]) {
+  const int N = E + 1;
+  long o = 0, s = 0, g = 0, eo = 0;
+  for (int i = 0; i < N; ++i) {
+    const long n = sd[i];
+    node_off[i] = o;
+    o += n * n + 3 * n;
+    sol_node_off[i] = s;
+    s += 2 * n;
+  }
+  for (int e = 0; e < E; ++e) {
+    const long np = sd[parents[e]], nc = sd[children[e]], m = cd[e];
+    edge_off[e] = eo;
+    eo += nc * np + nc * m + np * m + m * m + m;
+    sol_edge_off[e] = s;
+    s += m;
+    gains_off[e] = g;
+    g += m * np + m;
+  }
+  lens[0] = o;
+  lens[1] = eo;
+  lens[2] = s;
+  lens[3] = g;
+}
+
+/* The parents / children of the layout: only valid edges are read. */
+static int tree_edges_valid(int E, const int *parents, const int *children) {
+  if (parents == NULL || children == NULL)
+    return 0;
+  for (int e = 0; e < E; ++e)
+    if (parents[e] < 0 || parents[e] > E || children[e] < 0 || children[e] > E)
+      return 0;
+  return 1;
+}
+
+long lqr_oracle_tree_batch_len(int num_edges, const int *edge_parents,
+                               const int *edge_children, const int *state_dims,
+                               const int *control_dims, int which) {
+  const int E = num_edges, N = E + 1;
+  if (which < 0 || which > 3 || !tree_edges_valid(E, edge_parents, edge_children))
+    return -1;
+  long *tab = (long *)malloc(sizeof(long) * (size_t)(2 * N + 3 * E + 1));
+  long lens[4];
+  tree_layout(E, edge_parents, edge_children, state_dims, control_dims, tab,
+              tab + N, tab + N + E, tab + 2 * N + E, tab + 2 * N + 2 * E, lens);
+  free(tab);
+  return lens[which];
+}
+
+int lqr_oracle_tree_batch(int num_edges, int root, const int *edge_parents,
+                          const int *edge_children, const int *state_dims,
+                          const int *control_dims, long batch,
+                          const double *nodes, const double *edges, double *sol,
+                          double *gains, int *status, int threads) {
+  const int E = num_edges, N = E + 1;
+  if (E < 0 || !tree_edges_valid(E, edge_parents, edge_children))
+    return -1;
+  long *tab = (long *)malloc(sizeof(long) * (size_t)(2 * N + 3 * E + 1));
+  long *node_off = tab, *edge_off = tab + N, *sol_node_off = tab + N + E,
+       *sol_edge_off = tab + 2 * N + E, *gains_off = tab + 2 * N + 2 * E;
+  long lens[4];
+  tree_layout(E, edge_parents, edge_children, state_dims, control_dims,
+              node_off, edge_off, sol_node_off, sol_edge_off, gains_off, lens);
+  if (threads < 1)
+    threads = 1;
+#ifdef _OPENMP
+#pragma omp parallel num_threads(threads)
+#endif
+  {
+    lqr_oracle_problem prob;
+    lqr_oracle_workspace ws;
+    memset(&prob, 0, sizeof(prob));
+    double **ptrs = (double **)calloc((size_t)(7 * N + 6 * E + 2), sizeof(double *));
+    double **cur = ptrs;
+    prob.Q = cur, cur += N;
+    prob.q = cur, cur += N;
+    prob.c = cur, cur += N;
+    prob.delta = cur, cur += N;
+    prob.A = cur, cur += E;
+    prob.B = cur, cur += E;
+    prob.M = cur, cur += E;
+    prob.R = cur, cur += E;
+    prob.r = cur, cur += E;
+    double **x = cur, **y = cur + N, **u = cur + 2 * N;
+    prob.num_edges = E;
+    prob.root = root;
+    prob.edge_parents = edge_parents;
+    prob.edge_children = edge_children;
+    prob.state_dims = state_dims;
+    prob.control_dims = control_dims;
+    lqr_oracle_workspace_reserve(&ws, &prob);
+    lqr_oracle_compile_topology(&prob, &ws);
+#ifdef _OPENMP
+#pragma omp for schedule(static)
+#endif
+    for (long p = 0; p < batch; ++p) {
+      /* The reference takes non-const double** (lqr.hpp:76-85); it only
+       * reads. */
+      double *np_ = (double *)nodes + p * lens[0];
+      double *ep = (double *)edges + p * lens[1];
+      double *sp = sol + p * lens[2];
+      for (int i = 0; i < N; ++i) {
+        const long n = state_dims[i];
+        double *b = np_ + node_off[i];
+        prob.Q[i] = b;
+        prob.q[i] = b + n * n;
+        prob.c[i] = b + n * n + n;
+        prob.delta[i] = b + n * n + 2 * n;
+        x[i] = sp + sol_node_off[i];
+        y[i] = sp + sol_node_off[i] + n;
+      }
+      for (int e = 0; e < E; ++e) {
+        const long npar = state_dims[edge_parents[e]],
+                   nc = state_dims[edge_children[e]], m = control_dims[e];
+        double *b = ep + edge_off[e];
+        prob.A[e] = b;
+        prob.B[e] = b + nc * npar;
+        prob.M[e] = b + nc * npar + nc * m;
+        prob.R[e] = b + nc * npar + nc * m + npar * m;
+        prob.r[e] = b + nc * npar + nc * m + npar * m + m * m;
+        u[e] = sp + sol_edge_off[e];
+      }
+      status[p] = lqr_oracle_factor(&prob, &ws);
+      if (status[p] != LQR_ORACLE_SUCCESS)
+        continue;
+      lqr_oracle_solve(&prob, &ws, x, u, y);
+      if (gains != NULL) {
+        double *gp = gains + p * lens[3];
+        for (int e = 0; e < E; ++e) {
+          const long npar = state_dims[edge_parents[e]], m = control_dims[e];
+          memcpy(gp + gains_off[e], ws.K[e], sizeof(double) * (size_t)(m * npar));
+          memcpy(gp + gains_off[e] + m * npar, ws.k[e], sizeof(double) * (size_t)m);
+        }
+      }
+    }
+    lqr_oracle_workspace_free(&ws);
+    free(ptrs);
+  }
+  free(tab);
+  return 0;
+}

@@ -103,6 +103,37 @@ long lqr_oracle_chain_mats_len(int n, int m, int T);
 long lqr_oracle_chain_vecs_len(int n, int m, int T);
 long lqr_oracle_chain_gains_len(int n, int m, int T);
 
+/*
+ * Batched tree convenience used by the full-batch parity tests: `batch`
+ * problems of ONE topology (lqr.hpp:5-64), threads > 1: an OpenMP loop over
+ * problems, one workspace per thread.  Per problem p, every block
+ * column-major and compact, n_i = state_dims[i], m_e = control_dims[e],
+ * np_e / nc_e = state_dims of the parent / child of edge e:
+ *
+ *   nodes[p]: for node i in 0..E : Q_i (n_i*n_i) | q_i | c_i | delta_i (n_i)
+ *   edges[p]: for edge e in 0..E-1 : A_e (nc_e*np_e) | B_e (nc_e*m_e) |
+ *                                    M_e (np_e*m_e) | R_e (m_e*m_e) | r_e (m_e)
+ *   sol[p]  : for node i : x_i (n_i) | y_i (n_i), then for edge e : u_e (m_e)
+ *   gains[p]: for edge e : K_e (m_e*np_e) | k_e (m_e)     (gains may be NULL)
+ *   status[p]: FactorStatus of problem p, INVALID_TOPOLOGY for every problem
+ *              of a topology compile_topology rejects; sol/gains of a failed
+ *              problem are left untouched.
+ *
+ * Returns 0, or -1 (nothing written) when a parent or child index lies
+ * outside 0..E, where the layout itself is undefined.
+ */
+int lqr_oracle_tree_batch(int num_edges, int root, const int *edge_parents,
+                          const int *edge_children, const int *state_dims,
+                          const int *control_dims, long batch,
+                          const double *nodes, const double *edges, double *sol,
+                          double *gains, int *status, int threads);
+
+/* Length (in scalars) of one problem's nodes (which = 0), edges (1), sol (2)
+ * or gains (3) in the packed tree layout; -1 as lqr_oracle_tree_batch. */
+long lqr_oracle_tree_batch_len(int num_edges, const int *edge_parents,
+                               const int *edge_children, const int *state_dims,
+                               const int *control_dims, int which);
+
 #ifdef __cplusplus
 }
 #endif

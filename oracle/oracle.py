@@ -100,6 +100,10 @@ def _bind(L):
         L.lqr_oracle_solve.restype = None
         L.lqr_oracle_chain_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long] + \
             [ctypes.c_void_p] * 5 + [ctypes.c_int]
+        L.lqr_oracle_tree_batch.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4 + \
+            [ctypes.c_long] + [ctypes.c_void_p] * 5 + [ctypes.c_int]
+        L.lqr_oracle_tree_batch_len.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int]
+        L.lqr_oracle_tree_batch_len.restype = ctypes.c_long
         for name in ("mats", "vecs", "gains"):
             fn = getattr(L, f"lqr_oracle_chain_{name}_len")
             fn.argtypes = [ctypes.c_int] * 3
@@ -213,4 +217,56 @@ def chain_batch(n, m, T, mats, vecs, threads=1, want_gains=True, native=False):
     status = np.zeros(batch, dtype=np.int32)
     L.lqr_oracle_chain_batch(n, m, T, batch, mats.ctypes.data, vecs.ctypes.data, sol.ctypes.data,
                              gains.ctypes.data if want_gains else None, status.ctypes.data, threads)
+    return sol, gains, status
+
+
+class TreeBatchLayout:
+    """Offsets of the packed tree layout of lqr_oracle_tree_batch (lqr_oracle.h): for one topology,
+    node_off[i] / edge_off[e] into a problem's `nodes` / `edges` row, x_off[i] (y_i follows x_i) and
+    u_off[e] into its `sol` row, gains_off[e] (k_e follows K_e) into its `gains` row; *_len are the row
+    lengths."""
+
+    def __init__(self, parents, children, state_dims, control_dims):
+        sd, cd = list(state_dims), list(control_dims)
+        self.node_off, self.x_off, self.edge_off, self.u_off, self.gains_off = [], [], [], [], []
+        o = s = 0
+        for n in sd:
+            self.node_off.append(o)
+            o += n * n + 3 * n
+            self.x_off.append(s)
+            s += 2 * n
+        eo = g = 0
+        for e, m in enumerate(cd):
+            np_, nc = sd[parents[e]], sd[children[e]]
+            self.edge_off.append(eo)
+            eo += nc * np_ + nc * m + np_ * m + m * m + m
+            self.u_off.append(s)
+            s += m
+            self.gains_off.append(g)
+            g += m * np_ + m
+        self.nodes_len, self.edges_len, self.sol_len, self.gains_len = o, eo, s, g
+
+
+def tree_batch(parents, children, state_dims, control_dims, nodes, edges, threads=1, root=0, want_gains=True):
+    """Run the oracle over `batch` problems of one tree (lqr_oracle_tree_batch): nodes, edges numpy float64
+    [batch, len] in the packed tree layout (TreeBatchLayout).  Returns sol, gains (None unless want_gains),
+    status; sol / gains rows of failed problems stay zero."""
+    L = lib()
+    E = len(control_dims)
+    par, ch = _int_array(list(parents)), _int_array(list(children))
+    sd, cd = _int_array(list(state_dims)), _int_array(list(control_dims))
+    lens = [L.lqr_oracle_tree_batch_len(E, par, ch, sd, cd, w) for w in range(4)]
+    if min(lens) < 0:
+        raise ValueError("edge index outside the tree")
+    nodes = np.ascontiguousarray(nodes, dtype=np.float64)
+    edges = np.ascontiguousarray(edges, dtype=np.float64)
+    batch = nodes.shape[0]
+    assert nodes.shape == (batch, lens[0]) and edges.shape == (batch, lens[1]), (nodes.shape, edges.shape, lens)
+    sol = np.zeros((batch, lens[2]))
+    gains = np.zeros((batch, lens[3])) if want_gains else None
+    status = np.zeros(batch, dtype=np.int32)
+    rc = L.lqr_oracle_tree_batch(E, root, par, ch, sd, cd, batch, nodes.ctypes.data, edges.ctypes.data,
+                                 sol.ctypes.data, gains.ctypes.data if want_gains else None, status.ctypes.data,
+                                 threads)
+    assert rc == 0
     return sol, gains, status
