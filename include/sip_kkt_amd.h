@@ -130,6 +130,16 @@ size_t sip_kkt_work_bytes(const sip_kkt_plan *plan);
  * or "tree:general".  The string belongs to the plan; sip_kkt_plan_set_theta appends to it (" + fused theta passes"),
  * so a pointer obtained before that call must be fetched again after it. */
 const char *sip_kkt_kernel_name(const sip_kkt_plan *plan);
+/* Opt-in (on = 1): on a valid tree or non-uniform-chain plan whose tree fits a size class of the fused tree kernels
+ * (state dims <= 15, control dims <= 8; not with SIP_LQR_TREE=general), the Riccati part of sip_kkt_factor,
+ * sip_kkt_solve, sip_kkt_factor_solve, the factor of sip_kkt_factor_theta and the solves of sip_kkt_solve_theta run
+ * sip_lqr_tree_factor_fused / sip_lqr_tree_solve_fused instead of the general engine; sip_kkt_work_bytes then includes
+ * their scratch, and the kernel name starts "tree:fused <sip_lqr_tree_split_kernel_name>" in place of "tree:general".  Call once, right after
+ * sip_kkt_plan_create, before sip_kkt_work_bytes is read and before sip_kkt_plan_set_theta.  On chain plans and
+ * larger trees it returns SIP_LQR_OK and changes nothing (the name stays "chain:..." / "tree:general"); on = 0
+ * changes nothing.  SIP_LQR_ERR_INVALID_ARGUMENT: NULL plan, or called after sip_kkt_plan_set_theta or a second
+ * time with on = 1. */
+int sip_kkt_plan_set_tree_fused(sip_kkt_plan *plan, int on);
 
 /* Replaces CallbackProvider::factor (helpers.cpp:242-370): checks and inverts
  * the regularization, condenses the constraint Jacobians into Q_mod / M_mod /

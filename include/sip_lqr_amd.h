@@ -332,6 +332,30 @@ int sip_lqr_tree_factor_solve_workspace(const sip_lqr_tree_plan *plan, const dou
                                         void *d_scratch, void *stream);
 const char *sip_lqr_tree_kernel_name(const sip_lqr_tree_plan *plan);
 
+/* The two halves of the fused sweep, as the reference calls them (CallbackProvider::factor / ::solve,
+ * helpers.cpp:368, 826): exactly the data contracts of sip_lqr_tree_factor() / sip_lqr_tree_solve() on the
+ * size-class kernels.  sip_lqr_tree_factor_fused() reads Q, M, R, A, B, delta (never q, r, c), writes W, K, G_factor
+ * per edge and V, F_factor, sqrt_delta, sqrt_delta_inv per node to d_work (same layout and conventions as
+ * sip_lqr_tree_factor_solve_workspace()) and the statuses to d_status (first failing node / edge in postorder, G
+ * before delta before F at a node); it does not touch an output arena.  sip_lqr_tree_solve_fused() reads q, c, r
+ * (and A, B, delta) from d_input and the factor state from d_work, writes x, y, u to d_output and v per node, k per
+ * edge to d_work -- nothing else of d_work; instances whose d_status != SUCCESS are skipped, their outputs untouched.
+ * May be called repeatedly after one factor.  A factor from sip_lqr_tree_factor(),
+ * sip_lqr_tree_factor_solve_workspace() or sip_lqr_tree_factor_fused() serves sip_lqr_tree_solve(),
+ * sip_lqr_tree_solve_fused() and sip_lqr_tree_solve_multi() alike.  d_scratch: sip_lqr_tree_fused_scratch_bytes()
+ * bytes (0: general engine, may be NULL).  Trees beyond the size classes and plans created with
+ * SIP_LQR_TREE=general run sip_lqr_tree_factor() / sip_lqr_tree_solve() themselves.  A latched invalid topology:
+ * sip_lqr_tree_factor_fused() reports it as sip_lqr_tree_factor() does, sip_lqr_tree_solve_fused() returns
+ * SIP_LQR_ERR_INVALID_ARGUMENT, as it does for a missing pointer, before any HIP call.  Both only enqueue kernels
+ * on `stream` (no synchronisation, allocation or copy): graph-capturable.  sip_lqr_tree_split_kernel_name():
+ * "tree_factor_qw16<N,M>/f64 + tree_solve_qw16<N,M>/f64" (the FACTOR_ONLY instantiation of tree_qw16.hpp and the
+ * SINGLE one of tree_mrhs_qw16.hpp) or "tree_generic/f64"; "" for NULL. */
+int sip_lqr_tree_factor_fused(const sip_lqr_tree_plan *plan, const double *d_input, double *d_work,
+                              int32_t *d_status, void *d_scratch, void *stream);
+int sip_lqr_tree_solve_fused(const sip_lqr_tree_plan *plan, const double *d_input, double *d_work,
+                             double *d_output, const int32_t *d_status, void *d_scratch, void *stream);
+const char *sip_lqr_tree_split_kernel_name(const sip_lqr_tree_plan *plan);
+
 /* Replaces: the multi-right-hand-side block of solve_stagewise_kkt_matrix (helpers.cpp:414-747, its LQR part
  * :521-665: LQR::solve with GEMM in place of GEMV, reading LQR::Workspace directly; the caller is the theta Schur
  * complement K^-1 J_theta, helpers.cpp:387) on any tree, for num_rhs >= 1 columns against ONE factorization.

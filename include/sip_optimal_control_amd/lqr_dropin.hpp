@@ -379,6 +379,18 @@ public:
     general_engine_ = on;
     gpu_.reset();
   }
+  // With the fused size-class kernel: factor_with_status() runs the factorization alone (sip_lqr_tree_factor_fused)
+  // and solve() solves against the factor state it left on the device (sip_lqr_tree_solve_fused) without
+  // refactoring -- the reference's semantics: the factor state is that of the matrices at factor time.  Off (the
+  // default), solve() runs the whole fused factor + solve sweep again.  Also: SIP_LQR_DROPIN_SPLIT=1.
+  static bool &default_split_fused() {
+    static bool on = [] {
+      const char *v = std::getenv("SIP_LQR_DROPIN_SPLIT");
+      return v != nullptr && v[0] == '1';
+    }();
+    return on;
+  }
+  void set_split_fused(bool on) { split_fused_ = on; }
   bool uses_fused_tree_kernel() {
     OnDevice on_device(device_ordinal_);
     return traversal_status_ == FactorStatus::SUCCESS && fast_chain() == nullptr && device().d_scratch != nullptr;
@@ -413,7 +425,10 @@ public:
     Device &d = device();
     gather_input(d);
     d.h2d(d.d_in, d.h_in);
-    if (d.d_scratch != nullptr) // the fused size-class kernel, writing every LQR::Workspace field (tree_qw16.hpp)
+    if (d.d_scratch != nullptr && split_fused_) // the factorization alone on the size-class kernel
+      check(sip_lqr_tree_factor_fused(d.plan, d.d_in, d.d_ws, d.d_status, d.d_scratch, nullptr),
+            "sip_lqr_tree_factor_fused");
+    else if (d.d_scratch != nullptr) // the fused size-class kernel, writing every LQR::Workspace field (tree_qw16.hpp)
       check(sip_lqr_tree_factor_solve_workspace(d.plan, d.d_in, d.d_ws, d.d_out, d.d_status, d.d_scratch, nullptr),
             "sip_lqr_tree_factor_solve_workspace");
     else
@@ -434,7 +449,10 @@ public:
     Device &d = device();
     gather_input(d);
     d.h2d(d.d_in, d.h_in);
-    if (d.d_scratch != nullptr) // one fused sweep (it refactors: same matrices, same factor state)
+    if (d.d_scratch != nullptr && split_fused_) // against the device factor state of the last factor
+      check(sip_lqr_tree_solve_fused(d.plan, d.d_in, d.d_ws, d.d_out, d.d_status, d.d_scratch, nullptr),
+            "sip_lqr_tree_solve_fused");
+    else if (d.d_scratch != nullptr) // one fused sweep (it refactors: same matrices, same factor state)
       check(sip_lqr_tree_factor_solve_workspace(d.plan, d.d_in, d.d_ws, d.d_out, d.d_status, d.d_scratch, nullptr),
             "sip_lqr_tree_factor_solve_workspace");
     else
@@ -705,6 +723,7 @@ private:
   int device_ordinal_ = default_device();
   bool fused_chains_ = default_fused_chains();
   bool general_engine_ = default_general_engine();
+  bool split_fused_ = default_split_fused();
 };
 
 } // namespace sip::optimal_control

@@ -73,6 +73,9 @@ _SIGNATURES = {
     "sip_lqr_tree_solve_multi_scratch_bytes": (ctypes.c_size_t, [_P, ctypes.c_int]),
     "sip_lqr_tree_solve_multi": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
     "sip_lqr_tree_multi_kernel_name": (ctypes.c_char_p, [_P]),
+    "sip_lqr_tree_factor_fused": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
+    "sip_lqr_tree_solve_fused": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "sip_lqr_tree_split_kernel_name": (ctypes.c_char_p, [_P]),
     "sip_lqr_kernel_name": (ctypes.c_char_p, [_P]),
     "sip_lqr_version": (ctypes.c_char_p, []),
     # include/sip_kkt_amd.h
@@ -90,6 +93,7 @@ _SIGNATURES = {
     "sip_kkt_factor_solve": (ctypes.c_int, [_P] * 11),
     "sip_kkt_add_Kx_to_y": (ctypes.c_int, [_P] * 9),
     "sip_kkt_plan_set_theta": (ctypes.c_int, [_P, ctypes.c_int]),
+    "sip_kkt_plan_set_tree_fused": (ctypes.c_int, [_P, ctypes.c_int]),
     "sip_kkt_theta_len": (ctypes.c_size_t, [_P]),
     "sip_kkt_theta_offset": (ctypes.c_size_t, [_P, ctypes.c_int, ctypes.c_int]),
     "sip_kkt_theta_work_bytes": (ctypes.c_size_t, [_P]),

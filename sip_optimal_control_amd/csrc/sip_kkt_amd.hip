@@ -65,6 +65,10 @@ struct sip_kkt_plan {
   // tree plans: K^-1 J_theta through one sip_lqr_tree_solve_multi over all columns; SIP_KKT_THETA_TREE_MULTI=0
   // keeps the column-by-column sip_kkt_solve loop
   bool tree_theta_multi = false;
+  // tree plans: the Riccati factor / solve on sip_lqr_tree_factor_fused / sip_lqr_tree_solve_fused, their scratch at
+  // at_tree_scratch of d_work (sip_kkt_plan_set_tree_fused)
+  bool tree_fused = false;
+  size_t at_tree_scratch = 0;
   sipamd::kkt::ChainTheta ct{};
   size_t lds_theta_rhs = 0, lds_theta_recover = 0, lds_theta_dot = 0;
   bool staged = false; // LDS-staged kernels (false: items too large for LDS, or SIP_KKT_VARIANT=direct)
@@ -732,6 +736,23 @@ size_t sip_kkt_work_bytes(const sip_kkt_plan *p) {
 
 const char *sip_kkt_kernel_name(const sip_kkt_plan *p) { return p ? p->name.c_str() : ""; }
 
+int sip_kkt_plan_set_tree_fused(sip_kkt_plan *p, int on) {
+  if (p == nullptr || p->theta_dim != 0 || (on && p->tree_fused))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  if (!on || p->input_status != SIP_KKT_SUCCESS || p->tree == nullptr)
+    return SIP_LQR_OK; // chain plans (and plans without a Riccati back end): nothing to switch
+  const size_t scratch = sip_lqr_tree_fused_scratch_bytes(p->tree);
+  if (scratch == 0)
+    return SIP_LQR_OK; // beyond the size classes, or SIP_LQR_TREE=general: the general engine stays
+  p->tree_fused = true;
+  p->at_tree_scratch = p->work_bytes;
+  p->work_bytes = align256(p->work_bytes + scratch);
+  const std::string general = "tree:general"; // (what follows it, e.g. " + staged condensation", stays)
+  const std::string rest = p->name.compare(0, general.size(), general) == 0 ? p->name.substr(general.size()) : "";
+  p->name = std::string("tree:fused ") + sip_lqr_tree_split_kernel_name(p->tree) + rest;
+  return SIP_LQR_OK;
+}
+
 int sip_kkt_factor(const sip_kkt_plan *p, const double *d_model, const double *d_w, const double *d_r1,
                    const double *d_r2, const double *d_r3, void *d_work, int32_t *d_status, void *stream) {
   if (p == nullptr || d_status == nullptr)
@@ -749,8 +770,10 @@ int sip_kkt_factor(const sip_kkt_plan *p, const double *d_model, const double *d
   hipError_t e = launch_condense(p, r, d_model, d_w, d_r1, d_r2, d_r3, nullptr, s);
   if (e != hipSuccess)
     return report(e, "sip_kkt_factor(condense)");
-  const int rc = p->chain ? sip_lqr_factor(p->chain, r.in0, r.gain, d_status, r.lqr, s)
-                          : sip_lqr_tree_factor(p->tree, r.in0, (double *)r.lqr, d_status, s);
+  const int rc = p->chain        ? sip_lqr_factor(p->chain, r.in0, r.gain, d_status, r.lqr, s)
+                 : p->tree_fused ? sip_lqr_tree_factor_fused(p->tree, r.in0, (double *)r.lqr, d_status,
+                                                             (char *)d_work + p->at_tree_scratch, s)
+                                 : sip_lqr_tree_factor(p->tree, r.in0, (double *)r.lqr, d_status, s);
   if (rc != SIP_LQR_OK)
     return rc;
   return report(launch_merge(p, r, d_status, s), "sip_kkt_factor(status)");
@@ -773,8 +796,10 @@ int sip_kkt_solve(const sip_kkt_plan *p, const double *d_model, const double *d_
   hipError_t e = launch_rhs(p, r, d_model, d_b, d_status, s);
   if (e != hipSuccess)
     return report(e, "sip_kkt_solve(rhs)");
-  const int rc = p->chain ? sip_lqr_solve(p->chain, r.in0, r.in1, r.out, r.gain, r.lqr, s)
-                          : sip_lqr_tree_solve(p->tree, r.in0, (double *)r.lqr, r.out, d_status, s);
+  const int rc = p->chain        ? sip_lqr_solve(p->chain, r.in0, r.in1, r.out, r.gain, r.lqr, s)
+                 : p->tree_fused ? sip_lqr_tree_solve_fused(p->tree, r.in0, (double *)r.lqr, r.out, d_status,
+                                                            (char *)d_work + p->at_tree_scratch, s)
+                                 : sip_lqr_tree_solve(p->tree, r.in0, (double *)r.lqr, r.out, d_status, s);
   if (rc != SIP_LQR_OK)
     return rc;
   return report(launch_recover(p, r, d_model, d_b, d_sol, d_status, s), "sip_kkt_solve(recover)");

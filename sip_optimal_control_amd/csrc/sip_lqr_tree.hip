@@ -158,6 +158,7 @@ int sip_lqr_tree_plan_create(int64_t batch, int num_edges, int root,
         st.kind = 0;
         node_fields(st, j);
         edge_fields(st, g.child_edges[ci]);
+        st.ov = g.ov[st.child]; // (v of the child: read back by the single-rhs solve, tree_mrhs_qw16.hpp)
         st.flags = (ci == lo ? sipamd::TS_LOAD_V : 0) | (st.child == finished ? sipamd::TS_CHILD_LIVE : 0);
         steps.push_back(st);
         finished = -1;
@@ -403,6 +404,56 @@ int sip_lqr_tree_factor_solve(const sip_lqr_tree_plan *plan, const double *d_inp
 int sip_lqr_tree_factor_solve_workspace(const sip_lqr_tree_plan *plan, const double *d_input, double *d_work,
                                         double *d_output, int32_t *d_status, void *d_scratch, void *stream) {
   return tree_factor_solve_impl(plan, d_input, d_work, d_output, d_status, d_scratch, stream, true);
+}
+
+int sip_lqr_tree_factor_fused(const sip_lqr_tree_plan *plan, const double *d_input, double *d_work,
+                              int32_t *d_status, void *d_scratch, void *stream) {
+  if (plan == nullptr || d_status == nullptr)
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  if (plan->topology_status != SIP_LQR_SUCCESS || plan->fused == nullptr) // latched status / the general engine
+    return sip_lqr_tree_factor(plan, d_input, d_work, d_status, stream);
+  if ((d_input == nullptr && plan->g.in0_len > 0) || d_work == nullptr || d_scratch == nullptr)
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  sipamd::DeviceGuard on_device(plan->device);
+  if (on_device.err != hipSuccess)
+    return SIP_LQR_ERR_HIP;
+  char *w = (char *)d_scratch;
+  const hipError_t e = plan->fused->launch_factor(plan->sched, d_input, d_work, (double *)w, (double *)(w + plan->at_spill),
+                                                  d_status, (long)plan->batch, (hipStream_t)stream);
+  if (e != hipSuccess) {
+    std::fprintf(stderr, "sip_lqr_tree_factor_fused: %s\n", hipGetErrorString(e));
+    return SIP_LQR_ERR_HIP;
+  }
+  return SIP_LQR_OK;
+}
+
+int sip_lqr_tree_solve_fused(const sip_lqr_tree_plan *plan, const double *d_input, double *d_work, double *d_output,
+                             const int32_t *d_status, void *d_scratch, void *stream) {
+  if (plan == nullptr || d_status == nullptr || d_work == nullptr ||
+      (d_output == nullptr && plan->g.out_len > 0) || (d_input == nullptr && plan->g.in0_len > 0))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  if (plan->topology_status != SIP_LQR_SUCCESS)
+    return SIP_LQR_ERR_INVALID_ARGUMENT; // solve() needs a successful factor
+  if (plan->fused == nullptr)
+    return sip_lqr_tree_solve(plan, d_input, d_work, d_output, d_status, stream);
+  if (d_scratch == nullptr) // (unused by the solve, but part of the contract: the plan's fused scratch)
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  sipamd::DeviceGuard on_device(plan->device);
+  if (on_device.err != hipSuccess)
+    return SIP_LQR_ERR_HIP;
+  const hipError_t e = plan->fused->launch_solve(plan->sched, d_input, d_work, d_output, d_status, (long)plan->batch,
+                                                 (hipStream_t)stream);
+  if (e != hipSuccess) {
+    std::fprintf(stderr, "sip_lqr_tree_solve_fused: %s\n", hipGetErrorString(e));
+    return SIP_LQR_ERR_HIP;
+  }
+  return SIP_LQR_OK;
+}
+
+const char *sip_lqr_tree_split_kernel_name(const sip_lqr_tree_plan *plan) {
+  if (plan == nullptr)
+    return "";
+  return plan->fused != nullptr ? plan->fused->split_name : "tree_generic/f64";
 }
 
 } // extern "C"

@@ -28,6 +28,11 @@
 // q (n) | c (n), edge blocks r (m): the output arena's layout) and of the outputs (x | y, u) at
 // (col * batch + b) * out_len.  A launch of `ncols_launch` columns is a grid of (batch / 4) x
 // ceil(ncols_launch / P) single-wave workgroups: wavefront (b, y) carries columns [y P, y P + P).
+//
+// SINGLE (P = 1; tree_solve_qw16, sip_lqr_tree_solve_fused): LQR::solve itself (lqr.cpp:735-871), with the contract
+// of sip_lqr_tree_solve: q, c and r come from the INPUT arena (rhs_all is not read), v per node and k per edge go
+// to their LQR::Workspace slots of the work arena, which cols_all then points at (the other fields of that arena
+// are only read, through work_all).  The backward records of edge steps carry the CHILD's v offset in `ov`.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,12 +45,13 @@ struct TreeColLayout {
   __host__ __device__ static long len(const TreeSchedule &ts) { return (long)ts.Nn * N + (long)ts.E * M; } // per column and problem
 };
 
-template <int N, int M, int P>
+template <int N, int M, int P, bool SINGLE = false>
 __global__ __launch_bounds__(64) void tree_solve_mrhs_qw16(
     const TreeSchedule ts, const double *__restrict__ in_all, const double *__restrict__ work_all,
     const double *__restrict__ rhs_all, double *out_all, double *cols_all, const int *__restrict__ status,
     const long batch, const int ncols_launch) {
   static_assert(N >= 1 && N <= 16 && M >= 1 && M <= 16 && P >= 1 && P <= 16, "");
+  static_assert(!SINGLE || P == 1, "one right-hand side");
   const int col0 = (int)blockIdx.y * P;
   const int ncols = ncols_launch - col0 < P ? ncols_launch - col0 : P;
   const int lane = threadIdx.x & 63, c = lane & 15, rr = lane >> 4;
@@ -60,9 +66,16 @@ __global__ __launch_bounds__(64) void tree_solve_mrhs_qw16(
   const double *wk = work_all + p * ts.ws_len;
   // column col of this group: base + col * stride
   const long io_stride = batch * ts.out_len, cl_stride = batch * CL;
-  const double *rhs = rhs_all + ((long)col0 * batch + p) * ts.out_len;
+  const double *rhs = SINGLE ? in : rhs_all + ((long)col0 * batch + p) * ts.out_len;
   double *out = out_all + ((long)col0 * batch + p) * ts.out_len;
-  double *cl = cols_all + ((long)col0 * batch + p) * CL;
+  double *cl = cols_all + (SINGLE ? p * ts.ws_len : ((long)col0 * batch + p) * CL);
+  // where q of a node, c of a child, r of an edge (in `rhs`), v of a node and k of an edge (in `cl`) are
+  auto off_q = [](const TreeStep &st) { return SINGLE ? st.oq : st.oxp; };
+  auto off_cc = [](const TreeStep &st) { return SINGLE ? st.odc - st.nc : st.oyc; }; // input arena: c | delta
+  auto off_r = [](const TreeStep &st) { return SINGLE ? st.orr : st.ou; };
+  auto off_vc = [](const TreeStep &st) { return SINGLE ? st.ov : (long)st.child * N; };
+  auto off_vn = [](const TreeStep &st) { return SINGLE ? st.ov : (long)st.node * N; };
+  auto off_k = [&](const TreeStep &st) { return SINGLE ? st.ok : KOFF + (long)st.edge * M; };
 
   // Element (r, k) of the column-major rows x cols block at `off` of arena `a` (0 outside it): the
   // load is issued unconditionally from a clamped address (the arena's first scalar, always readable)
@@ -119,7 +132,7 @@ __global__ __launch_bounds__(64) void tree_solve_mrhs_qw16(
       sfor<0, P>([&](auto cc) {
         constexpr int col = decltype(cc)::value;
         if (col < ncols)
-          o.qv[col] = at(rhs + col * io_stride, st.oxp, n, 1, c, 0); // q of `node` (the x slot of the layout)
+          o.qv[col] = at(rhs + col * io_stride, off_q(st), n, 1, c, 0); // q of `node` (the x slot of the layout)
       });
     if (st.kind != 0)
       return;
@@ -135,9 +148,9 @@ __global__ __launch_bounds__(64) void tree_solve_mrhs_qw16(
     sfor<0, P>([&](auto cc) {
       constexpr int col = decltype(cc)::value;
       if (col < ncols) {
-        o.cv[col] = at(rhs + col * io_stride, st.oyc, nc, 1, c, 0); // c of the child (the y slot)
-        o.rv[col] = at(rhs + col * io_stride, st.ou, m, 1, c, 0);   // r of the edge (the u slot)
-        o.vc[col] = at(cl + col * cl_stride, (long)st.child * N, nc, 1, c, 0);
+        o.cv[col] = at(rhs + col * io_stride, off_cc(st), nc, 1, c, 0); // c of the child (the y slot)
+        o.rv[col] = at(rhs + col * io_stride, off_r(st), m, 1, c, 0);   // r of the edge (the u slot)
+        o.vc[col] = at(cl + col * cl_stride, off_vc(st), nc, 1, c, 0);
       }
     });
   };
@@ -150,7 +163,7 @@ __global__ __launch_bounds__(64) void tree_solve_mrhs_qw16(
     if (st.flags & TS_LOAD_V) // v = q  (lqr.cpp:744)
       sfor<0, P>([&](auto cc) { v[decltype(cc)::value] = o.qv[decltype(cc)::value]; });
     if (st.kind == 0) { // one child edge of `node` (lqr.cpp:776-794)
-      const long ko = KOFF + (long)st.edge * M;
+      const long ko = off_k(st);
       sfor<0, P>([&](auto cc) {
         constexpr int col = decltype(cc)::value;
         if (col < ncols) {
@@ -174,7 +187,7 @@ __global__ __launch_bounds__(64) void tree_solve_mrhs_qw16(
       sfor<0, P>([&](auto cc) {
         constexpr int col = decltype(cc)::value;
         if (col < ncols)
-          cl[col * cl_stride + (long)st.node * N + c] = v[col];
+          cl[col * cl_stride + off_vn(st) + c] = v[col];
       });
     }
   }
@@ -191,7 +204,7 @@ __global__ __launch_bounds__(64) void tree_solve_mrhs_qw16(
     sfor<0, P>([&](auto cc) {
       constexpr int col = decltype(cc)::value;
       if (col < ncols) {
-        const double cr = at(rhs + col * io_stride, ts.root_oy, n, 1, c, 0);
+        const double cr = at(rhs + col * io_stride, SINGLE ? ts.root_od - n : ts.root_oy, n, 1, c, 0);
         const double f = dl * v[col] - cr;
         const double x = -sd * llt_solve(NN{}, Lr, Lc, li, sdi * f); // F_inv_mult_vector  (lqr.cpp:531-549)
         double ay[4] = {v[col], 0.0, 0.0, 0.0};
@@ -219,14 +232,14 @@ __global__ __launch_bounds__(64) void tree_solve_mrhs_qw16(
     sfor<0, M>([&](auto jj) { o.Br[decltype(jj)::value] = at(in, st.oB, nc, m, c, decltype(jj)::value); });
     load_L(NN{}, st.oF, nc, o.Lr, o.Lc, o.li);
     o.sd = at(wk, st.osd, nc, 1, c, 0), o.sdi = at(wk, st.osdi, nc, 1, c, 0), o.dl = at(in, st.odc, nc, 1, c, 0);
-    const long ko = KOFF + (long)st.edge * M;
+    const long ko = off_k(st);
     sfor<0, P>([&](auto cc) {
       constexpr int col = decltype(cc)::value;
       if (col < ncols) {
         o.xp[col] = at(out + col * io_stride, st.oxp, n, 1, c, 0); // x of the parent (written by this lane)
         o.kk[col] = at(cl + col * cl_stride, ko, m, 1, c, 0);
-        o.cc[col] = at(rhs + col * io_stride, st.oyc, nc, 1, c, 0);
-        o.vc[col] = at(cl + col * cl_stride, (long)st.child * N, nc, 1, c, 0);
+        o.cc[col] = at(rhs + col * io_stride, off_cc(st), nc, 1, c, 0);
+        o.vc[col] = at(cl + col * cl_stride, off_vc(st), nc, 1, c, 0);
       }
     });
   };

@@ -26,13 +26,31 @@ hipError_t launch_multi(const TreeSchedule &ts, const double *input, const doubl
                      dim3(64), 0, s, ts, input, work, rhs_cols, out_cols, cols, (const int *)status, batch, num_rhs);
   return hipGetLastError();
 }
+// the factorization alone, every factor-state field into the work arena (tree_factor_qw16: sip_lqr_tree_factor_fused)
+template <int N, int M>
+hipError_t launch_factor(const TreeSchedule &ts, const double *input, double *work, double *pgains, double *spill,
+                         int32_t *status, long batch, hipStream_t s) {
+  hipLaunchKernelGGL((tree_factor_solve_qw16<N, M, true, true>), dim3((unsigned)((batch + 3) / 4)), dim3(64), 0, s, ts,
+                     input, (double *)nullptr, work, pgains, spill, (int *)status, batch);
+  return hipGetLastError();
+}
+// one right-hand side against the factor state of the work arena, v and k into it (tree_solve_qw16:
+// sip_lqr_tree_solve_fused)
+template <int N, int M>
+hipError_t launch_solve(const TreeSchedule &ts, const double *input, double *work, double *output,
+                        const int32_t *status, long batch, hipStream_t s) {
+  hipLaunchKernelGGL((tree_solve_mrhs_qw16<N, M, 1, true>), dim3((unsigned)((batch + 3) / 4)), dim3(64), 0, s, ts, input,
+                     (const double *)work, input, output, work, (const int *)status, batch, 1);
+  return hipGetLastError();
+}
 template <int N, int M>
 long cols_len(const TreeSchedule &ts) {
   return TreeColLayout<N, M>::len(ts);
 }
 #define TREE_CLASS(N, M)                                                                                            \
   {N, M, "tree_factor_solve_qw16<" #N "," #M ">/f64", &launch<N, M, false>, &launch<N, M, true>,                    \
-   "tree_solve_mrhs_qw16<" #N "," #M ">/f64", &launch_multi<N, M>, &cols_len<N, M>}
+   "tree_solve_mrhs_qw16<" #N "," #M ">/f64", &launch_multi<N, M>, &cols_len<N, M>,                                  \
+   "tree_factor_qw16<" #N "," #M ">/f64 + tree_solve_qw16<" #N "," #M ">/f64", &launch_factor<N, M>, &launch_solve<N, M>}
 // sorted by cost: the first class that holds the largest node and the largest control wins
 // ((9, 3): the reference's variable-shape benchmark family at base dimension 8 -- states 7..9, controls 1..3,
 // benchmarks/lqr_benchmark.cpp:209-310 -- padded to (10, 4) before round 3)

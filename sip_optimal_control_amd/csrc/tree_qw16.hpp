@@ -100,13 +100,20 @@ struct TreeLayout {
 // EXPORT: also write W, G_factor (edges) and V, F_factor, sqrt_delta, sqrt_delta_inv, v (nodes) of LQR::Workspace
 // into the work arena (which must then be given): a second instantiation, so that the kernel behind
 // sip_lqr_tree_factor_solve keeps its registers.
-template <int N, int M, bool EXPORT = false>
+// FACTOR_ONLY (with EXPORT; tree_factor_qw16, sip_lqr_tree_factor_fused): the backward sweep alone, writing exactly
+// what sip_lqr_tree_factor writes -- W, K, G_factor per edge, V, F_factor, sqrt_delta, sqrt_delta_inv per node, the
+// statuses.  q, r and c are never read: the affine lane N starts from zeros (so it carries zeros, and costs no
+// register: it is one lane of the row), k, v, the padded gains, the affine spill and the output arena are not
+// written, and there is no rollout.
+template <int N, int M, bool EXPORT = false, bool FACTOR_ONLY = false>
 __global__ __launch_bounds__(64) void tree_factor_solve_qw16(
     const TreeSchedule ts, const double *__restrict__ in_all, double *__restrict__ out_all,
     double *__restrict__ work_all /* may be null: K, k not wanted */, double *__restrict__ gains,
     double *__restrict__ wsp, int *__restrict__ status, const long batch) {
   static_assert(N >= 1 && N <= 15, "one lane of the row carries the affine column");
   static_assert(M >= 1 && M <= 16, "");
+  static_assert(EXPORT || !FACTOR_ONLY, "the factor-only sweep leaves its result in the work arena");
+  constexpr bool AFF = !FACTOR_ONLY; // the affine column is loaded, spilled and stored
   using L = TreeLayout<N, M>;
   const int lane = threadIdx.x & 63, c = lane & 15, rr = lane >> 4;
   long p = (long)blockIdx.x * 4 + rr;
@@ -201,8 +208,9 @@ __global__ __launch_bounds__(64) void tree_factor_solve_qw16(
   auto fetch = [&](const TreeStep &st, Pre &o) {
     const int n = st.n, nc = st.nc, m = st.m;
     if (st.flags & TS_LOAD_V) { // [Q | q] of `node`; identity columns on the padding lanes
-      const double *src = isV ? in + st.oq : in + st.oQ;
-      load_col(o.v, src, n, isV ? 1 : n, isV ? 0 : c, isM || isV, E);
+      const bool qv = AFF & isV;
+      const double *src = qv ? in + st.oq : in + st.oQ;
+      load_col(o.v, src, n, qv ? 1 : n, qv ? 0 : c, isM || qv, E);
     }
     if (st.kind == 0) {
       // column c of R (identity on the padding), column c of M^T = row c of M; vector lane: r
@@ -214,7 +222,7 @@ __global__ __launch_bounds__(64) void tree_factor_solve_qw16(
         constexpr int q = decltype(jj)::value;
         const int qq = (anyR & (q < m)) ? q : 0;
         const double rl = Rc[qq], ml = Mr[(long)(anyM ? n : 0) * qq], rr_ = rv[qq];
-        const double unit = (q == c) ? 1.0 : 0.0, mz = (c < n) ? ml : 0.0, hv = isV ? rr_ : mz;
+        const double unit = (q == c) ? 1.0 : 0.0, mz = (c < n) ? ml : 0.0, hv = (AFF & isV) ? rr_ : mz;
         const bool inR = (q < m) & (c < m);
         o.g[q] = inR ? rl : unit;
         o.h[q] = (q < m) ? hv : 0.0;
@@ -223,7 +231,7 @@ __global__ __launch_bounds__(64) void tree_factor_solve_qw16(
       load_col(o.b, in + st.oB, nc, m, c, true, ZERO); // column c of B (nc x m)
       o.dl = load_elem(in + st.odc, nc, c, true, 1.0); // delta of the child
     } else {
-      load_col(o.a, in + st.oc, n, 1, 0, isV, ZERO); // c on the vector lane
+      load_col(o.a, in + st.oc, n, 1, 0, AFF & isV, ZERO); // c on the vector lane
       load_col(o.b, in + st.od, n, 1, 0, isV, ZERO); // delta on the vector lane
       o.dl = load_elem(in + st.od, n, c, true, 1.0);
     }
@@ -273,7 +281,7 @@ __global__ __launch_bounds__(64) void tree_factor_solve_qw16(
         });
       }
       rank1x<N, N, true>(F, W, Aaug); // [F | g] = W [A | t] + [0 | v]  (lqr.cpp:703, :780-781)
-      if (valid && isV)
+      if (AFF && valid && isV)
         sfor<0, N>([&](auto ii) { slot[N * N + decltype(ii)::value] = F[decltype(ii)::value]; }); // g of the child
       // H_child = B^T W (lqr.cpp:692); G = R + H_child B (:693-694)
       sfor<0, M>([&](auto jj) { Hc[decltype(jj)::value] = 0.0; });
@@ -303,10 +311,11 @@ __global__ __launch_bounds__(64) void tree_factor_solve_qw16(
       sfor<0, M>([&](auto jj) { K[decltype(jj)::value] = -K[decltype(jj)::value]; });
       if (valid && c <= N) {
         double *gi = pg + (long)e * L::GAIN + c * M;
-        sfor<0, M>([&](auto jj) { gi[decltype(jj)::value] = K[decltype(jj)::value]; });
+        if constexpr (AFF) // (the rollout's copy)
+          sfor<0, M>([&](auto jj) { gi[decltype(jj)::value] = K[decltype(jj)::value]; });
         if (work != nullptr) { // LQR::Workspace::K (m x n, column-major) and k of the caller's work arena
           double *dst = isV ? work + st.ok : work + st.oK + (long)m * c;
-          if (isV || c < n)
+          if ((AFF & isV) || c < n)
             sfor<0, M>([&](auto jj) {
               constexpr int q = decltype(jj)::value;
               if (q < m)
@@ -331,7 +340,7 @@ __global__ __launch_bounds__(64) void tree_factor_solve_qw16(
         tv[r] = pre.a[r] - pre.b[r] * V[r]; // c - delta o v on the vector lane, zeros elsewhere
         Vc[r] = V[r];
       });
-      if (valid && isV)
+      if (AFF && valid && isV)
         sfor<0, N>([&](auto ii) {
           constexpr int r = decltype(ii)::value;
           mine[N * N + 2 * N + r] = tv[r];
@@ -362,7 +371,7 @@ __global__ __launch_bounds__(64) void tree_factor_solve_qw16(
             }
           });
         }
-        if (valid && isV)
+        if (AFF && valid && isV)
           sfor<0, N>([&](auto ii) {
             constexpr int r = decltype(ii)::value;
             if (r < n)
@@ -373,7 +382,7 @@ __global__ __launch_bounds__(64) void tree_factor_solve_qw16(
       }
       if (stat == 0 && ffail)
         stat = 2; // F_FACTORIZATION_FAILURE
-      if (valid && isV) // h = S D^{-1/2} (c - delta o v)
+      if (AFF && valid && isV) // h = S D^{-1/2} (c - delta o v)
         sfor<0, N>([&](auto ii) { mine[N * N + N + decltype(ii)::value] = X[decltype(ii)::value]; });
       if (valid && isM)
         sfor<0, N>([&](auto ii) { mine[c * N + decltype(ii)::value] = X[decltype(ii)::value]; });
@@ -426,7 +435,7 @@ __global__ __launch_bounds__(64) void tree_factor_solve_qw16(
 #endif
   }
   // root (the last node step): g = v + W (c - delta o v)  (lqr.cpp:798-819)
-  {
+  if constexpr (AFF) {
     double F[N];
     sfor<0, N>([&](auto ii) { F[decltype(ii)::value] = isV ? Vc[decltype(ii)::value] : 0.0; });
     rank1x<N, N, true>(F, W, tv);
@@ -437,6 +446,8 @@ __global__ __launch_bounds__(64) void tree_factor_solve_qw16(
   }
   if (valid && c == 0)
     status[p] = stat;
+  if constexpr (FACTOR_ONLY)
+    return;
   // the rollout reads S / g / h / K / k written above by other lanes of this wave
   __syncthreads();
 

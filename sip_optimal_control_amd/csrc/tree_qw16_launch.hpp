@@ -24,6 +24,15 @@ struct TreeClass {
                              double *out_cols, double *cols, const int32_t *status, long batch, int num_rhs,
                              hipStream_t s);
   long (*cols_len)(const TreeSchedule &ts);
+  // the two halves of LQR::factor_with_status + LQR::solve as separate sweeps (sip_lqr_tree_factor_fused /
+  // sip_lqr_tree_solve_fused): the factorization alone (FACTOR_ONLY instantiation of tree_qw16.hpp), and one
+  // right-hand side from the input arena against the factor state of the work arena, v and k written into it
+  // (SINGLE instantiation of tree_mrhs_qw16.hpp)
+  const char *split_name;
+  hipError_t (*launch_factor)(const TreeSchedule &ts, const double *input, double *work, double *pgains,
+                              double *spill, int32_t *status, long batch, hipStream_t s);
+  hipError_t (*launch_solve)(const TreeSchedule &ts, const double *input, double *work, double *output,
+                             const int32_t *status, long batch, hipStream_t s);
 };
 
 // Smallest size class that holds a tree whose largest state / control dimensions are max_n / max_m;

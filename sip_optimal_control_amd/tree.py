@@ -101,16 +101,45 @@ class BatchedTreeLQR:
         workspace=True: every LQR::Workspace field of `work` (sip_lqr_tree_factor_solve_workspace)."""
         s = torch.cuda.current_stream(self.device)
         entry = self._lib.sip_lqr_tree_factor_solve_workspace if workspace else self._lib.sip_lqr_tree_factor_solve
-        need = self._lib.sip_lqr_tree_fused_scratch_bytes(self._plan)
-        if getattr(self, "_scratch", None) is None or self._scratch.numel() < need:
-            self._scratch = torch.empty(max(1, need), dtype=torch.uint8, device=self.device)
+        scratch = self._fused_scratch()
         _check(entry(self._plan, ctypes.c_void_p(self.input.data_ptr()),
                      ctypes.c_void_p(self.work.data_ptr()),
                      ctypes.c_void_p(self.output.data_ptr()),
                      ctypes.c_void_p(self.status.data_ptr()),
-                     ctypes.c_void_p(self._scratch.data_ptr()),
+                     scratch,
                      ctypes.c_void_p(s.cuda_stream)), "sip_lqr_tree_factor_solve")
         return self.output, self.status
+
+    def _fused_scratch(self):
+        need = self._lib.sip_lqr_tree_fused_scratch_bytes(self._plan)
+        if getattr(self, "_scratch", None) is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(max(1, need), dtype=torch.uint8, device=self.device)
+        return ctypes.c_void_p(self._scratch.data_ptr())
+
+    @property
+    def split_kernel_name(self):
+        return self._lib.sip_lqr_tree_split_kernel_name(self._plan).decode()
+
+    def factor_fused(self):
+        """factor_with_status() alone on the size-class kernel (sip_lqr_tree_factor_fused): the factor state of
+        sip_lqr_tree_factor in `work`, statuses; q, r, c are not read and `output` is not written."""
+        s = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_tree_factor_fused(self._plan, ctypes.c_void_p(self.input.data_ptr()),
+                                                   ctypes.c_void_p(self.work.data_ptr()),
+                                                   ctypes.c_void_p(self.status.data_ptr()), self._fused_scratch(),
+                                                   ctypes.c_void_p(s.cuda_stream)), "sip_lqr_tree_factor_fused")
+        return self.status
+
+    def solve_fused(self):
+        """solve() on the size-class kernel (sip_lqr_tree_solve_fused) against the factor state in `work`: x, u, y
+        to `output`, v and k to `work`; problems whose status != 0 are skipped."""
+        s = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_tree_solve_fused(self._plan, ctypes.c_void_p(self.input.data_ptr()),
+                                                  ctypes.c_void_p(self.work.data_ptr()),
+                                                  ctypes.c_void_p(self.output.data_ptr()),
+                                                  ctypes.c_void_p(self.status.data_ptr()), self._fused_scratch(),
+                                                  ctypes.c_void_p(s.cuda_stream)), "sip_lqr_tree_solve_fused")
+        return self.output
 
     def solve(self):
         s = torch.cuda.current_stream(self.device)
