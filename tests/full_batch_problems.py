@@ -5,7 +5,13 @@ Every block is a numpy array with a leading batch axis (blocks["Q"][i] is [B, n_
 index per arena: into the packed tree layout of the oracle (oracle.TreeBatchLayout / lqr_oracle_tree_batch) and
 into the input arena of a BatchedTreeLQR plan (by its sip_lqr_tree_offset table).  Gathers map the plan's
 output / work / multi-rhs arenas back onto the oracle's sol and gains layout.
+
+newton_kkt_batch draws B distinct Newton-KKT problems (model and theta arenas, regularization, right-hand side) the
+same way, one vectorised draw per block (tests/test_gpu_kkt_family.py).
 """
+import math
+import os
+
 import numpy as np
 
 from oracle.oracle import TreeBatchLayout
@@ -204,3 +210,88 @@ def assert_discriminates(ref, tol, rows=None, what=""):
         ok = (q >= 0) & (q < B)
         gap = np.abs(ref[rows[ok]] - ref[q[ok]]).max(axis=1) / scale[ok]
         assert gap.min() >= 1e3 * tol, (what, d, float(gap.min()), int(rows[ok][gap.argmin()]))
+
+
+def oracle_threads():
+    """Threads for the CPU oracle: the smallest of OMP_NUM_THREADS (when set), the CPUs this process may run on,
+    and 16 (os.cpu_count() reports the whole host, not what the process may use)."""
+    n = min(16, len(os.sched_getaffinity(0)))
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "").split(",")[0]))
+    except ValueError:
+        pass
+    return max(1, n)
+
+
+# ---- Newton-KKT problems ------------------------------------------------------------------------------------------
+def newton_kkt_batch(dims, B, seed, r2_max=1e2, device="cpu"):
+    """B distinct Newton-KKT problems on `dims` (an oracle.kkt.KKTDims, any tree / dimensions, with or without
+    theta), with the value distributions of reference_kkt_problems.newton_kkt_problem (newton_kkt_benchmark.cpp
+    :170-262): dc / dg Jacobians 0.1 N(0,1), node d2L_dx2 = S^T S + 1e-3 I, ddyn_dx = I + 0.05 N(0,1), ddyn_du
+    0.1 N(0,1), edge d2L_dx2 = 0, d2L_dxdu 0.01 N(0,1), d2L_du2 = S^T S + I; theta couplings 1e-3 N(0,1),
+    d2L_dtheta2 = S^T S + 100 I on the last node and 0 elsewhere; r2 log-uniform [1e-3, r2_max], w [1e-2, 1e3],
+    r3 [1e-3, 1e1], r1 = 1e-8, rhs N(0,1).  Every block is one draw with a leading batch axis, placed at the
+    offsets of dims (the plan's model_offset / theta_offset tables).
+
+    Returns float64 torch tensors on `device`, each [B, len]: (model, w, r1, r2, r3, rhs), and theta_model when
+    dims.p > 0 (then r1 and rhs include the theta columns, as for BatchedNewtonKKT.factor_theta / solve_theta)."""
+    import torch
+    from oracle.kkt import EDGE_BLOCKS, NODE_BLOCKS, THETA_EDGE_BLOCKS, THETA_NODE_BLOCKS
+    f64 = torch.float64
+    gen = torch.Generator(device=device)
+    gen.manual_seed(seed)
+
+    def randn(rows, cols, scale):
+        return scale * torch.randn(B, rows, cols, generator=gen, device=device, dtype=f64)
+
+    def spd(k, shift):
+        S = randn(k, k, 1.0)
+        return S.transpose(1, 2) @ S + shift * torch.eye(k, device=device, dtype=f64)
+
+    def put(arena, off, mat):  # [B, rows, cols] -> column-major block at off
+        if mat.shape[1] * mat.shape[2]:
+            arena[:, off:off + mat.shape[1] * mat.shape[2]] = mat.transpose(1, 2).reshape(B, -1)
+
+    def edge_eye(nc, np_):
+        return torch.eye(nc, np_, device=device, dtype=f64).expand(B, nc, np_)
+
+    model = torch.zeros(B, max(1, dims.model_len), dtype=f64, device=device)
+    node_draw = {"d2L_dx2": lambda n, c, g: spd(n, 1e-3), "dc_dx": lambda n, c, g: randn(c, n, 0.1),
+                 "dg_dx": lambda n, c, g: randn(g, n, 0.1)}
+    for i in range(dims.N):
+        for b in NODE_BLOCKS:
+            put(model, dims.node_off[b][i], node_draw[b](dims.sd[i], dims.ncd[i], dims.ngd[i]))
+    for e in range(dims.E):
+        np_, nc, m = dims.sd[dims.parents[e]], dims.sd[dims.children[e]], dims.cd[e]
+        for b, (r, c) in zip(EDGE_BLOCKS, dims.edge_shapes(e)):
+            if b == "d2L_dx2":
+                continue  # 0
+            mat = spd(m, 1.0) if b == "d2L_du2" else \
+                edge_eye(nc, np_) + randn(nc, np_, 0.05) if b == "ddyn_dx" else \
+                randn(r, c, 0.01 if b == "d2L_dxdu" else 0.1)
+            put(model, dims.edge_off[b][e], mat)
+
+    def logu(lo, hi, length):
+        u = torch.rand(B, length, generator=gen, device=device, dtype=f64)
+        return torch.exp(math.log(lo) + (math.log(hi) - math.log(lo)) * u)
+
+    r2 = logu(1e-3, r2_max, dims.y_dim)
+    w = logu(1e-2, 1e3, dims.z_dim)
+    r3 = logu(1e-3, 1e1, dims.z_dim)
+    r1 = torch.full((B, dims.x_dim + dims.p), 1e-8, dtype=f64, device=device)
+    rhs = torch.randn(B, dims.full_dim, generator=gen, device=device, dtype=f64)
+    out = [model, w, r1, r2, r3, rhs]
+    if dims.p > 0:
+        theta = torch.zeros(B, max(1, dims.theta_len), dtype=f64, device=device)
+        for i in range(dims.N):
+            for b, (r, c) in zip(THETA_NODE_BLOCKS, dims.theta_node_shapes(i)):
+                if b != "d2L_dtheta2":
+                    put(theta, dims.theta_node_off[b][i], randn(r, c, 1e-3))
+                elif i == dims.E:
+                    put(theta, dims.theta_node_off[b][i], spd(dims.p, 100.0))
+        for e in range(dims.E):
+            for b, (r, c) in zip(THETA_EDGE_BLOCKS, dims.theta_edge_shapes(e)):
+                if b != "d2L_dtheta2":
+                    put(theta, dims.theta_edge_off[b][e], randn(r, c, 1e-3))
+        out.append(theta)
+    return tuple(out)

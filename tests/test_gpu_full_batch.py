@@ -14,7 +14,6 @@ Tolerances are those of the existing tests of each kernel: 1e-10 relative to the
 (test_gpu_kkt_tree_theta.py), 1e-4 for fp32 against the oracle on the fp32-rounded problem
 (test_gpu_mf32_parity.py).  The worst measured error of every comparison is printed."""
 import functools
-import os
 import zlib
 
 import numpy as np
@@ -27,7 +26,7 @@ from oracle.kkt import KKTDims, KKTOracle
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-THREADS = max(1, min(32, os.cpu_count() or 1))
+THREADS = fb.oracle_threads()
 BATCHES = [4096, 4093]
 TREE_TOL = 1e-10
 F_SENTINEL = -3.0e33
