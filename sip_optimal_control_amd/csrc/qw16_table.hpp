@@ -1,0 +1,57 @@
+// qw16_table.hpp -- the table entry of the dedicated chain kernels and the slices of the fp64 fused kernels
+// (qw16_kernels.hip), for the host code that looks kernels up (sip_lqr_amd.hip): no kernel source in here.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/sip_lqr_amd.h"
+// the manifest of gen_qw16_kernels.py: slice count, slice list, the entries of each slice
+#ifndef SIP_QW16_MANIFEST // tools/ab_build.sh, tools/diag_build.sh: a one-slice manifest of their own
+#define SIP_QW16_MANIFEST "qw16_kernels_gen.hpp"
+#endif
+#include SIP_QW16_MANIFEST
+
+#ifdef SIP_LQR_STAMPS
+// Diagnostic build: device buffer of 8 x u64 per wave, set by the tool (sip_lqr_amd.hip).
+extern unsigned long long *g_sip_lqr_stamps;
+#define SIP_STAMP_PASS , g_sip_lqr_stamps
+#else
+#define SIP_STAMP_PASS
+#endif
+
+namespace sipamd {
+
+// mode: 0 fused factor + solve, 1 factor only (+ the G factors to gfac), 2 solve only
+typedef hipError_t (*launch_fs_t)(long batch, int T, const void *mats, const void *vecs, void *sol, void *gains,
+                                  int32_t *status, void *ws, hipStream_t stream, int mode, void *gfac);
+
+// LQR::solve for `ncols` right-hand sides in one sweep (chain_mrhs.hpp); columns `col_stride` scalars apart
+typedef hipError_t (*launch_mrhs_t)(long batch, int T, const void *mats, const void *vecs_cols, void *sol_cols,
+                                    const void *gains, const void *ws, const void *gfac, void *cws,
+                                    const int32_t *status, int ncols, long col_stride, hipStream_t stream);
+constexpr int kMrhsColumns = 8; // columns one multi-rhs launch carries
+
+// The split form of the fused sweep (sip_lqr_factor_solve_split): mats carries [Q | delta | M | R] per
+// stage, A | B stream from `ab` (scalars: ab + p * ab_pstride + i * ab_sstride).
+typedef hipError_t (*launch_split_t)(long batch, int T, const void *mats, const void *ab, long ab_pstride,
+                                     long ab_sstride, const void *vecs, void *sol, void *gains, int32_t *status,
+                                     void *ws, hipStream_t stream);
+
+struct KernelEntry {
+  int dtype, n, m;
+  const char *name;
+  int ws_slot; // scalars of workspace per node
+  launch_fs_t launch_fs;
+  launch_mrhs_t launch_mrhs;   // nullptr: this shape solves several right-hand sides column by column
+  int layout;                  // SIP_LQR_LAYOUT_* of mats the kernel reads (0: the full squares)
+  bool core;                   // a slice entry that SIP_LQR_EXTRA=0 leaves visible
+  launch_split_t launch_split; // nullptr: no split form of this kernel
+};
+
+// slice s of qw16_kernels.hip defines qw16_slice_<s>: its share of the manifest's entries
+#define SIP_QW16_DECLARE_SLICE(S) const KernelEntry *qw16_slice_##S(int *count);
+QW16_FOR_EACH_SLICE(SIP_QW16_DECLARE_SLICE)
+#undef SIP_QW16_DECLARE_SLICE
+
+} // namespace sipamd

@@ -17,7 +17,7 @@
 #include "chain_mf32.hpp"
 #include "mt16_launch.hpp"
 #include "generic_plan.hpp"
-#include "qw16_launch.hpp"
+#include "qw16_table.hpp"
 #include "stream_fill.hpp"
 
 struct sip_lqr_plan {
@@ -32,6 +32,8 @@ struct sip_lqr_plan {
   sipamd::launch_fs_t launch_fs;
   // several right-hand sides per sweep (chain_mrhs.hpp); nullptr: column by column
   sipamd::launch_mrhs_t launch_mrhs = nullptr;
+  // the fused sweep with A | B read in place (sip_lqr_factor_solve_split); nullptr: the plan's kernel has no such form
+  sipamd::launch_split_t launch_split = nullptr;
   // General engine on the packed chain layout: serves shapes / dtypes without
   // a dedicated kernel and the split factor / solve entry points.  Tables are
   // laid out and uploaded at plan creation, so that the compute entry points
@@ -78,69 +80,42 @@ hipError_t launch_mf32(long batch, int T, const void *mats, const void *vecs, vo
 
 using sipamd::KernelEntry;
 
-// First match wins; SIP_LQR_VARIANT=direct|staged (tests, A/B timing) narrows
-// the search to kernels whose name carries that tag.
 // fp32, n = 32: one problem per wavefront, products on the matrix cores
 #define MF32(M)                                                                \
   { SIP_LQR_F32, 32, M, "chain_factor_solve_mf32<32," #M ",mfma>/f32",          \
     sipamd::mf32::Layout<M>::WSN, &launch_mf32<M> }
 
+// n = 32 on 16 x 16 matrix-core tiles (chain_mt16.hpp), fp32 and fp64; the 32x32x2 kernel of round 1
+// (chain_mf32.hpp) stays selectable by SIP_LQR_VARIANT=mf32 for A/B timing
 const KernelEntry kKernels[] = {
-#if defined(SIP_QW16_QUICK) && defined(SIP_QW16_QUICK_C4) // tools/ab_build.sh: one kernel alone, for A/B timing
-    MT16_ENTRY(SIP_LQR_F32, float, "f32", 8), MF32(8),
-#elif defined(SIP_QW16_QUICK) && defined(SIP_QW16_QUICK_DIRECT)
-    QW16_STAGED(14, 8), QW16_STAGED(15, 4), QW16_STAGED(13, 5), QW16_STAGED(12, 8), QW16_STAGED(14, 4), QW16_STAGED(12, 6),
-#elif defined(SIP_QW16_QUICK) && defined(SIP_QW16_QUICK_MR) // ... with its multi-right-hand-side solve
-    QW16_STAGED_MR(12, 4),
-#elif defined(SIP_QW16_QUICK)
-    QW16_STAGED(12, 4),
-#else
-    // n = 32 on 16 x 16 matrix-core tiles (chain_mt16.hpp), fp32 and fp64; the 32x32x2 kernel of round 1
-    // (chain_mf32.hpp) stays selectable by SIP_LQR_VARIANT=mf32 for A/B timing
-    MT16_ENTRY(SIP_LQR_F32, float, "f32", 8), MT16_ENTRY(SIP_LQR_F32, float, "f32", 4),
+    MT16_ENTRY(SIP_LQR_F32, float, "f32", 8),  MT16_ENTRY(SIP_LQR_F32, float, "f32", 4),
     MT16_ENTRY(SIP_LQR_F64, double, "f64", 8), MT16_ENTRY(SIP_LQR_F64, double, "f64", 4),
-    // symmetric-packed layout (sip_lqr_plan_create_layout): found only by plans that ask for it
-    QW16_STAGED_SYM(12, 4), QW16_STAGED_SYM(8, 4), QW16_STAGED_SYM(4, 4),
-    MF32(8), QW16_STAGED_MR(12, 4), QW16_STAGED_MR(4, 2), QW16_DIRECT_MR(12, 4),
-    QW16_DIRECT_MR(4, 2),  QW16_STAGED_MR(1, 1), QW16_STAGED_MR(2, 1),
-    QW16_STAGED_MR(3, 2),  QW16_STAGED_MR(8, 3),
-    // the grid of the reference's benchmarks (lqr_benchmark.cpp:537-545,
-    // newton_kkt_benchmark.cpp:264-273: n in {4, 6, 8}, m in {1, 2, 3, 4}; n = 16 has no
-    // vector lane left and runs on the general engine) and n = 12 with fewer controls
-    QW16_STAGED_MR(4, 4),  QW16_STAGED_MR(6, 2),  QW16_STAGED_MR(6, 4),  QW16_STAGED_MR(8, 2),
-    QW16_STAGED_MR(8, 4),  QW16_STAGED_MR(12, 2), QW16_STAGED_MR(4, 1),  QW16_STAGED_MR(4, 3),
-    QW16_STAGED_MR(6, 1),  QW16_STAGED_MR(6, 3),  QW16_STAGED_MR(8, 1),  QW16_STAGED_MR(12, 1),
-    QW16_STAGED_MR(12, 3),
-    // hosts for the embedding of larger shapes (n <= 15: one lane of the row carries the affine column)
-    QW16_STAGED_MR(8, 8),  QW16_STAGED_MR(12, 8), QW16_STAGED_MR(14, 4), QW16_STAGED_MR(14, 8), QW16_STAGED_MR(15, 4),
-    QW16_STAGED_MR(15, 8),
-    // n = 16 (in the reference's benchmark grid): distributed-vector mode, see chain_qw16.hpp
-    QW16_DIRECT_MR(16, 1), QW16_DIRECT_MR(16, 2), QW16_DIRECT_MR(16, 3), QW16_DIRECT_MR(16, 4), QW16_DIRECT_MR(16, 8),
-#endif
+    MF32(8),
 };
 
-// Every other shape n <= 16, m <= 8 (qw16_extra.hip, compiled in SIP_QW16_SLICES slices).
-// SIP_LQR_EXTRA=0 (tests of the embedding) hides them.
+// kKernels, then the fused fp64 kernels of every shape n <= 16, m <= 8 (the slices of qw16_kernels.hip, where
+// the alternatives of a shape stand together, the default first).  SIP_LQR_EXTRA=0 (tests of the embedding)
+// hides those outside the core set.
 template <typename F> void for_each_kernel(F &&f) {
   for (const auto &k : kKernels)
     f(k);
-#ifndef SIP_QW16_NO_EXTRA
   const char *extra = std::getenv("SIP_LQR_EXTRA");
-  if (extra != nullptr && extra[0] == '0')
-    return;
+  const bool core_only = extra != nullptr && extra[0] == '0';
   typedef const KernelEntry *(*slice_fn)(int *);
-  static const slice_fn slices[sipamd::kQw16ExtraSlices] = {
-      sipamd::qw16_extra_slice_0, sipamd::qw16_extra_slice_1, sipamd::qw16_extra_slice_2, sipamd::qw16_extra_slice_3,
-      sipamd::qw16_extra_slice_4, sipamd::qw16_extra_slice_5, sipamd::qw16_extra_slice_6, sipamd::qw16_extra_slice_7};
+#define SIP_QW16_SLICE_FN(S) sipamd::qw16_slice_##S,
+  static const slice_fn slices[QW16_SLICE_COUNT] = {QW16_FOR_EACH_SLICE(SIP_QW16_SLICE_FN)};
+#undef SIP_QW16_SLICE_FN
   for (const slice_fn fn : slices) {
     int count = 0;
     const KernelEntry *table = fn(&count);
     for (int e = 0; e < count; ++e)
-      f(table[e]);
+      if (table[e].core || !core_only)
+        f(table[e]);
   }
-#endif
 }
 
+// First match wins; SIP_LQR_VARIANT=direct|staged (tests, A/B timing) narrows
+// the search to kernels whose name carries that tag.
 const KernelEntry *find_kernel(int dtype, int n, int m, int layout = SIP_LQR_LAYOUT_FULL) {
   const char *want = std::getenv("SIP_LQR_VARIANT");
   const KernelEntry *found = nullptr;
@@ -153,7 +128,8 @@ const KernelEntry *find_kernel(int dtype, int n, int m, int layout = SIP_LQR_LAY
 }
 
 // Smallest fused fp64 kernel that can embed an (n, m) chain: least N, then a staged kernel with
-// the least M, then a direct one.
+// the least M, then a direct one.  Called when no visible kernel has the shape itself: what can still hold
+// it is in kKernels or, with SIP_LQR_EXTRA=0, the core set.
 const KernelEntry *find_embedding_kernel(int n, int m) {
   const KernelEntry *best = nullptr;
   auto better = [&](const KernelEntry &k) {
@@ -166,9 +142,10 @@ const KernelEntry *find_embedding_kernel(int n, int m) {
       return ks;
     return k.m < best->m;
   };
-  for (const auto &k : kKernels)
+  for_each_kernel([&](const KernelEntry &k) {
     if (k.dtype == SIP_LQR_F64 && k.layout == SIP_LQR_LAYOUT_FULL && k.n >= n && k.m >= m && better(k))
       best = &k;
+  });
   return best;
 }
 
@@ -439,6 +416,7 @@ int sip_lqr_plan_create_layout(int dtype, int64_t batch, int T, int n, int m, in
   p->ws_slot = k ? k->ws_slot : 0;
   p->launch_fs = k ? k->launch_fs : nullptr;
   p->launch_mrhs = (k != nullptr && !p->padded) ? k->launch_mrhs : nullptr;
+  p->launch_split = (k != nullptr && !p->padded) ? k->launch_split : nullptr;
   p->solve_only = k != nullptr && k->dtype == SIP_LQR_F64 && k->n <= 16; // qw16 only (mt16 re-runs the sweep)
   const char *split = std::getenv("SIP_LQR_SPLIT");
   p->split_on_fused = p->launch_fs != nullptr && (layout != SIP_LQR_LAYOUT_FULL || !(split && std::strcmp(split, "general") == 0));
@@ -658,22 +636,18 @@ int sip_lqr_factor_solve(const sip_lqr_plan *plan, const void *d_mats,
   return report(e, "sip_lqr_factor_solve(general)");
 }
 
-// The fused sweep with A | B read in place (chain_qw16.hpp, SPLIT; qw16_split.hip).
-int sip_lqr_has_split(const sip_lqr_plan *plan) {
-  return plan != nullptr && plan->dtype == SIP_LQR_F64 && !plan->padded && plan->launch_fs != nullptr &&
-                 plan->kernel_name != nullptr && std::strstr(plan->kernel_name, "staged") != nullptr &&
-                 sipamd::find_split_launch(plan->n, plan->m, plan->layout) != nullptr
-             ? 1
-             : 0;
-}
+// The fused sweep with A | B read in place (chain_qw16.hpp, SPLIT): staged fp64 kernels have it, for the plan's
+// own shape only (not through the embedding).
+int sip_lqr_has_split(const sip_lqr_plan *plan) { return plan != nullptr && plan->launch_split != nullptr ? 1 : 0; }
 
 int64_t sip_lqr_split_mats_len(const sip_lqr_plan *plan) {
   if (plan == nullptr)
     return 0;
   const bool sym = plan->layout == SIP_LQR_LAYOUT_SYMMETRIC;
-  const long node = (sym ? (long)plan->n * (plan->n + 1) / 2 : (long)plan->n * plan->n) + plan->n;
-  return (int64_t)(plan->T + 1) * node +
-         (int64_t)plan->T * (sipamd::split_mats_stage(plan->n, plan->m, plan->layout) - node);
+  const int64_t n = plan->n, m = plan->m;
+  const int64_t node = (sym ? n * (n + 1) / 2 : n * n) + n;   // Q | delta
+  const int64_t rest = n * m + (sym ? m * (m + 1) / 2 : m * m); // M | R
+  return (plan->T + 1) * node + plan->T * rest;
 }
 
 int sip_lqr_factor_solve_split(const sip_lqr_plan *plan, const void *d_mats, const void *d_ab,
@@ -694,9 +668,8 @@ int sip_lqr_factor_solve_split(const sip_lqr_plan *plan, const void *d_mats, con
   sipamd::DeviceGuard on_device(plan->device);
   if (on_device.err != hipSuccess)
     return report(on_device.err, "sip_lqr_factor_solve_split(hipSetDevice)");
-  const sipamd::launch_split_t launch = sipamd::find_split_launch(plan->n, plan->m, plan->layout);
-  return report(launch(plan->batch, plan->T, d_mats, d_ab, (long)ab_problem_stride, (long)ab_stage_stride, d_vecs,
-                       d_sol, d_gains, d_status, d_workspace, (hipStream_t)stream),
+  return report(plan->launch_split(plan->batch, plan->T, d_mats, d_ab, (long)ab_problem_stride, (long)ab_stage_stride,
+                                   d_vecs, d_sol, d_gains, d_status, d_workspace, (hipStream_t)stream),
                 "sip_lqr_factor_solve_split");
 }
 

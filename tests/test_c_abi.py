@@ -91,7 +91,7 @@ def test_kernel_selection_and_embedding(lib, monkeypatch):
             kernel, _ = name(n, m)
             assert f"qw16<{n},{m}," in kernel and "embedding" not in kernel
             assert "staged" in kernel  # odd m too: pieces from 8-byte-aligned sources, gains by dwords
-    # every fp64 shape n <= 16, m <= 8 has an exact kernel (qw16_extra.hip); LDS-staged wherever its images fit a
+    # every fp64 shape n <= 16, m <= 8 has an exact kernel (qw16_kernels.hip); LDS-staged wherever its images fit a
     # workgroup's 64 KiB: all n <= 15; n = 16 (distributed-vector mode) stays on direct loads
     for n in range(1, 17):
         for m in range(1, 9):

@@ -50,7 +50,7 @@ def test_general_engine_fp64_matches_oracle(oracle_lib, monkeypatch, n, m, T, ba
     (5, 3, 0, 2, "<6,3,staged>"), (13, 4, 10, 6, "<14,4,staged>"), (13, 5, 8, 5, "<14,8,staged>"),
     (10, 6, 8, 5, "<12,8,staged>"), (15, 3, 5, 3, "<15,4,staged>"), (16, 6, 6, 5, "<16,8,direct>")])
 def test_embedding_in_the_next_fused_kernel(oracle_lib, monkeypatch, n, m, T, batch, host):
-    """Without the exact kernels of qw16_extra.hip (SIP_LQR_EXTRA=0; diagnostic builds leave them
+    """Without the exact kernels outside the core set (SIP_LQR_EXTRA=0; diagnostic builds leave them
     out) a uniform shape runs on the next larger fused kernel: the extra states and controls
     decouple exactly, so the real components match the oracle as usual.  Fused and split entry
     points, one failing problem."""
@@ -80,7 +80,7 @@ def test_embedding_in_the_next_fused_kernel(oracle_lib, monkeypatch, n, m, T, ba
 
 @pytest.mark.parametrize("n", list(range(1, 17)))
 def test_every_shape_up_to_16x8_has_an_exact_kernel(oracle_lib, n):
-    """qw16_extra.hip: every fp64 chain shape n <= 16, m <= 8 runs on its own instantiation of the
+    """qw16_kernels.hip: every fp64 chain shape n <= 16, m <= 8 runs on its own instantiation of the
     fused kernel (staged when n and m are even, n <= 14).  Fused and split entry points against
     the oracle, one problem with an indefinite R (G failure) in the batch."""
     from sip_optimal_control_amd import BatchedChainLQR, ChainShape

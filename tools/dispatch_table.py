@@ -1,0 +1,30 @@
+#!/usr/bin/env python3
+"""Print which kernel every chain plan gets: one line per dtype, n <= 33, m <= 9, layout and dispatch
+environment.  Needs no GPU (plans are created host-side); SIP_LQR_LIB picks the library.  Two builds
+dispatch alike exactly when their outputs are equal:  tools/dispatch_table.py > a.txt ; diff a.txt b.txt"""
+import ctypes
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from sip_optimal_control_amd._lib import load_library  # noqa: E402
+
+ENVS = [{}] + [{"SIP_LQR_VARIANT": v} for v in ("direct", "staged", "general", "mf32")]
+ENVS += [{"SIP_LQR_EXTRA": "0"}, {"SIP_LQR_EXTRA": "0", "SIP_LQR_PAD": "0"}, {"SIP_LQR_SPLIT": "general"}]
+KEYS = ("SIP_LQR_VARIANT", "SIP_LQR_EXTRA", "SIP_LQR_PAD", "SIP_LQR_SPLIT")
+
+lib = load_library()
+for env in ENVS:
+    for key in KEYS:  # the library reads them at plan creation
+        os.environ.pop(key, None)
+    os.environ.update(env)
+    tag = " ".join(f"{k}={v}" for k, v in env.items()) or "default"
+    for dtype, layout, n, m in ((d, l, n, m) for d in (0, 1) for l in (0, 1) for n in range(1, 34) for m in range(1, 10)):
+        plan = ctypes.c_void_p()
+        rc = lib.sip_lqr_plan_create_layout(dtype, 5, 7, n, m, 0, layout, ctypes.byref(plan))
+        row = [tag, "f32" if dtype else "f64", "sym" if layout else "full", n, m, rc]
+        if rc == 0:
+            row += [lib.sip_lqr_kernel_name(plan).decode(), lib.sip_lqr_workspace_bytes(plan), lib.sip_lqr_has_split(plan),
+                    lib.sip_lqr_split_mats_len(plan), lib.sip_lqr_solve_multi_workspace_bytes(plan, 8)]
+            lib.sip_lqr_plan_destroy(plan)
+        print(*row, sep="\t")
