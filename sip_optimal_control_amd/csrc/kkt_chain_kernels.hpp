@@ -47,10 +47,15 @@ typedef double d2_t __attribute__((ext_vector_type(2)));
 // nodes none.  Kernels instantiated with FN > 0 take every dimension but the horizon from the template: the index
 // arithmetic, the loops over constraint rows and most of the branches of the generic code fold away (the
 // condensation is issue-bound: ~2 400 instructions per stage in the generic form).  FN = 0: dimensions from `ck`.
+// The family's equality / inequality rows per edge and at the terminal node (sip_kkt_plan_create holds a plan's
+// dimensions against the same two).
+constexpr __host__ __device__ int family_c(const int n) { return n / 2 > 0 ? n / 2 : 1; }
+constexpr __host__ __device__ int family_g(const int m) { return 2 * m > 0 ? 2 * m : 1; }
+
 template <int FN, int FM>
 __device__ __forceinline__ ChainKkt family_dims(ChainKkt ck) {
   if constexpr (FN > 0) {
-    constexpr int c = FN / 2 > 0 ? FN / 2 : 1, g = 2 * FM > 0 ? 2 * FM : 1;
+    constexpr int c = family_c(FN), g = family_g(FM);
     constexpr int n = FN, m = FM;
     ck.n = n, ck.m = m, ck.cn = 0, ck.gn = 0, ck.cT = c, ck.gT = g, ck.ce = c, ck.ge = g;
     ck.node_len = n * n;

@@ -47,6 +47,10 @@ struct Meta {
   const long *oQ, *od, *oq, *oc, *ox, *oy, *oA, *oB, *oM, *oR, *orr, *ou;
 };
 
+// The kernels of kkt_kernels.hpp, kkt_theta_kernels.hpp and kkt_theta_chain_kernels.hpp that are no templates belong
+// to sip_kkt_amd.hip alone.  kkt_chain_kernels.hip, which includes these headers for the structs and device functions
+// the chain kernels use, defines SIP_KKT_CHAIN_UNIT and compiles without them.
+#ifndef SIP_KKT_CHAIN_UNIT
 // inv[0 .. y_dim) : dyn rows r2, constraint rows 1/r2; inv[y_dim ..) : 1/(w+r3).
 // regstat[p] != 0 iff any regularization of problem p is <= 0.
 __global__ void __launch_bounds__(256)
@@ -79,6 +83,7 @@ merge_status_kernel(const int *__restrict__ regstat, int32_t *__restrict__ statu
   if (p < batch && regstat[p] != 0)
     status[p] = code;
 }
+#endif
 
 // acc += sum_k (wgt[k] * Jb[k, cb]) * Ja[k, ca]   (J column-major, `rows` rows)
 __device__ __forceinline__ double rank_update(double acc, const double *Ja, int ca, const double *Jb, int cb,
@@ -88,6 +93,7 @@ __device__ __forceinline__ double rank_update(double acc, const double *Ja, int 
   return acc;
 }
 
+#ifndef SIP_KKT_CHAIN_UNIT
 __global__ void __launch_bounds__(TPB)
 condense_kernel(const Meta mt, const double *__restrict__ model_all, const double *__restrict__ r1_all,
                 const double *__restrict__ inv_all, double *__restrict__ in0_all, long batch) {
@@ -162,6 +168,7 @@ condense_kernel(const Meta mt, const double *__restrict__ model_all, const doubl
       Bm[idx] = B[idx];
   }
 }
+#endif
 
 // acc -= sum_k J[k, col] * (wgt[k] * rhs[k])   (subtract_weighted_jacobian_rhs, :138-153)
 __device__ __forceinline__ double sub_weighted(double acc, const double *J, int col, int rows,
@@ -171,6 +178,7 @@ __device__ __forceinline__ double sub_weighted(double acc, const double *J, int 
   return acc;
 }
 
+#ifndef SIP_KKT_CHAIN_UNIT
 __global__ void __launch_bounds__(TPB)
 rhs_kernel(const Meta mt, const double *__restrict__ model_all, const double *__restrict__ b_all,
            const double *__restrict__ inv_all, double *__restrict__ in1_all, const int32_t *__restrict__ status,
@@ -211,6 +219,7 @@ rhs_kernel(const Meta mt, const double *__restrict__ model_all, const double *__
     }
   }
 }
+#endif
 
 // row k of J x  (J column-major rows x cols)
 __device__ __forceinline__ double row_dot(const double *J, int k, int rows, int cols, const double *x) {
@@ -220,6 +229,7 @@ __device__ __forceinline__ double row_dot(const double *J, int k, int rows, int 
   return acc;
 }
 
+#ifndef SIP_KKT_CHAIN_UNIT
 __global__ void __launch_bounds__(TPB)
 recover_kernel(const Meta mt, const double *__restrict__ model_all, const double *__restrict__ b_all,
                const double *__restrict__ inv_all, const double *__restrict__ out_all,
@@ -272,6 +282,7 @@ recover_kernel(const Meta mt, const double *__restrict__ model_all, const double
     }
   }
 }
+#endif
 
 // ---------------------------------------------------------------------------
 // Staged variants: one workgroup per (problem, node).  The model item of the
@@ -317,6 +328,7 @@ __device__ __forceinline__ double sub_weighted_w(double acc, const double *J, in
   return acc;
 }
 
+#ifndef SIP_KKT_CHAIN_UNIT
 template <bool WITH_RHS>
 __global__ void __launch_bounds__(TPB)
 condense_staged_kernel(const Meta mt, const double *__restrict__ model_all, const double *__restrict__ r1_all,
@@ -588,6 +600,7 @@ recover_staged_kernel(const Meta mt, const double *__restrict__ model_all, const
     }
   }
 }
+#endif
 
 // column `col` of J^T v : sum_k J[k, col] v[k]
 __device__ __forceinline__ double col_dot(const double *J, int col, int rows, const double *v) {
@@ -612,6 +625,7 @@ struct ApplyIO {
   int parts;
 };
 
+#ifndef SIP_KKT_CHAIN_UNIT
 // y += K x (or the selected blocks of it), gather form: the lanes of a node item own the node's
 // state rows of y_x, its dynamics rows and node constraint rows of y_y, and its rows of y_z; the
 // lanes of an edge item own the control rows and the edge constraint rows.
@@ -741,6 +755,7 @@ apply_kernel(const Meta mt, const double *__restrict__ model_all, const double *
     }
   }
 }
+#endif
 
 } // namespace kkt
 } // namespace sipamd

@@ -379,6 +379,7 @@ theta_recover_chain_kernel(const ChainKkt ck_in, const ChainTheta ct, const doub
   }
 }
 
+#ifndef SIP_KKT_CHAIN_UNIT
 // S = sum of the stage partials (in stage order) + diag(r1_theta), then LLT in place (helpers.cpp:399-407).
 // One workgroup per problem.  LDS: p x p.
 __global__ void __launch_bounds__(TPB)
@@ -434,6 +435,7 @@ theta_schur_reduce_kernel(const int nstages, const int p, const int sx, const do
   for (int q = tid; q < pp; q += TPB)
     S_all[prob * pp + q] = sm[q];
 }
+#endif
 
 // The stage's share of J_theta^T v for a stagewise vector v = [x | y | z] (the solve: v = K^-1 b, helpers.cpp:920-928)
 // -> d_part[problem][stage][a].  LDS: [theta item | x_i|u_i rows of v (n + m) | dynamics rows of node i+1 (n) |
@@ -650,6 +652,7 @@ apply_theta_chain_kernel(const ChainKkt ck_in, const ChainTheta ct, const double
     }
 }
 
+#ifndef SIP_KKT_CHAIN_UNIT
 // theta = S^-1 (b_theta - J^T K^-1 b) with J^T K^-1 b from the stage partials; sol = K^-1 b - (K^-1 J) theta,
 // re-inserted as [x | theta | y | z]  (helpers.cpp:920-950).  One workgroup per problem.  LDS: p.
 __global__ void __launch_bounds__(TPB)
@@ -700,6 +703,7 @@ theta_finish_parts_kernel(const int nstages, const int p, const int sx, const lo
   for (int a = tid; a < p; a += TPB)
     sol[sx + a] = sm[a];
 }
+#endif
 
 } // namespace kkt
 } // namespace sipamd

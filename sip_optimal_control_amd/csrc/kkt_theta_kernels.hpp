@@ -40,6 +40,7 @@ __device__ __forceinline__ void put_rows(double *Jp, long col_stride, int at, co
   }
 }
 
+#ifndef SIP_KKT_CHAIN_UNIT
 // form_theta_jacobian, helpers.cpp:190-240.  One workgroup per (problem, node): the node's own
 // rows and the rows of its child edges (control, child dynamics, edge constraints).
 __global__ void __launch_bounds__(TPB)
@@ -376,6 +377,7 @@ apply_theta_kernel(const Meta mt, const ThetaMeta th, const double *__restrict__
   if (tid < p && (pH || pCT || pGT || pR))
     y_theta[tid] += pR ? yt + r1_all[prob * (sx + p) + sx + tid] * theta[tid] : yt;
 }
+#endif
 
 } // namespace kkt
 } // namespace sipamd

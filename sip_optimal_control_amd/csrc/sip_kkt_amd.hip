@@ -11,15 +11,22 @@
 #include <cstring>
 #include <new>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "generic_plan.hpp"
 #include "stream_fill.hpp"
-#include "kkt_chain_kernels.hpp"
-#include "kkt_kernels.hpp"
-#include "kkt_theta_kernels.hpp"
-#include "kkt_theta_chain_kernels.hpp"
+#include "kkt_chain_launch.hpp"
+
+const sipamd::kkt::KktChainKernels *sipamd::kkt::find_kkt_chain_kernels(const int n, const int m) {
+#define SIP_KKT_ROW_IF(N, M) \
+  if (n == N && m == M)      \
+    return &kkt_chain_row<N, M>;
+#define SIP_KKT_ROWS_IF(N) SIP_KKT_FAMILY_SHAPES(SIP_KKT_ROW_IF, N)
+  SIP_KKT_FAMILY_N(SIP_KKT_ROWS_IF)
+#undef SIP_KKT_ROWS_IF
+#undef SIP_KKT_ROW_IF
+  return &kkt_chain_row<0, 0>;
+}
 
 struct sip_kkt_plan {
   int64_t batch = 0;
@@ -43,10 +50,11 @@ struct sip_kkt_plan {
   // the fused step hands the Riccati sweep ddyn_dx | ddyn_du in the model arena instead of copying
   // them into its inputs (sip_lqr_factor_solve_split); SIP_KKT_SPLIT=0 keeps the copy
   bool chain_split = false;
-  // > 0: the plan's dimensions are those of the reference's Newton-KKT benchmark family for (n, m) =
-  // (family / 100, family % 100) -- the hot chain kernels then run as the instantiation that has every dimension
-  // but the horizon as a constant (kkt_chain_kernels.hpp: family_dims); SIP_KKT_FAMILY=0 keeps the generic kernels
-  int family = 0;
+  // the chain kernels the plan launches (kkt_chain_launch.hpp).  k->n > 0: the plan's dimensions are those of the
+  // reference's Newton-KKT benchmark family for (k->n, k->m) -- the hot chain kernels then run as the instantiation
+  // that has every dimension but the horizon as a constant (kkt_chain_kernels.hpp: family_dims); SIP_KKT_FAMILY=0
+  // keeps the generic kernels
+  const sipamd::kkt::KktChainKernels *k = sipamd::kkt::find_kkt_chain_kernels(0, 0);
   // ... and with Q_mod / R_mod as packed lower triangles (SIP_LQR_LAYOUT_SYMMETRIC) where the sweep has that kernel:
   // a second plan of the same shape, used by the fused step only; SIP_KKT_SYM=0 keeps the full squares
   sip_lqr_plan *chain_sym = nullptr;
@@ -168,25 +176,6 @@ bool uniform_constraints(const sip_kkt_plan &p) {
 }
 int even(int v) { return (v + 1) / 2 * 2; }
 
-// Calls f(integral_constant<FN>, integral_constant<FM>) for the plan's benchmark-family shape (family = 100 n + m),
-// f(0, 0) -- the generic kernels -- otherwise.
-template <class F> void family_dispatch(const int family, F &&f) {
-  auto at = [&](auto fn, auto fm) { f(fn, fm); };
-#define SIP_KKT_FAMILY_CASE(FN, FM)                                                      \
-  case 100 * FN + FM:                                                                    \
-    at(std::integral_constant<int, FN>{}, std::integral_constant<int, FM>{});           \
-    break;
-  switch (family) {
-    SIP_KKT_FAMILY_CASE(4, 1) SIP_KKT_FAMILY_CASE(4, 2) SIP_KKT_FAMILY_CASE(4, 3) SIP_KKT_FAMILY_CASE(4, 4)
-    SIP_KKT_FAMILY_CASE(6, 1) SIP_KKT_FAMILY_CASE(6, 2) SIP_KKT_FAMILY_CASE(6, 3) SIP_KKT_FAMILY_CASE(6, 4)
-    SIP_KKT_FAMILY_CASE(8, 1) SIP_KKT_FAMILY_CASE(8, 2) SIP_KKT_FAMILY_CASE(8, 3) SIP_KKT_FAMILY_CASE(8, 4)
-    SIP_KKT_FAMILY_CASE(12, 1) SIP_KKT_FAMILY_CASE(12, 2) SIP_KKT_FAMILY_CASE(12, 3) SIP_KKT_FAMILY_CASE(12, 4)
-  default:
-    at(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-  }
-#undef SIP_KKT_FAMILY_CASE
-}
-
 // b != nullptr (fused factor+solve on the staged kernels): also builds q_mod, r_mod, c_mod.
 // split (chain kernels only): mats for sip_lqr_factor_solve_split -- no A | B in it.
 hipError_t launch_condense(const sip_kkt_plan *p, const Regions &r, const double *model, const double *w,
@@ -226,32 +215,20 @@ hipError_t launch_condense(const sip_kkt_plan *p, const Regions &r, const double
     if (b != nullptr) {
       const double *bq = b + q0 * kkt_len;
       double *in1q = r.in1 + q0 * ck.vecs_len;
-      family_dispatch(p->family, [&](auto fn, auto fm) {
-        hipLaunchKernelGGL((sipamd::kkt::condense_chain_kernel<true, true, decltype(fn)::value, decltype(fm)::value>),
-                           dim3((unsigned)(nb * p->N)), dim3(sipamd::kkt::TPB), lds_chain, s, ck, mq, r1q, invq, in0q, bq,
-                           in1q, nb);
-      });
+      hipLaunchKernelGGL(p->k->condense_rhs, dim3((unsigned)(nb * p->N)), dim3(sipamd::kkt::TPB), lds_chain, s, ck, mq,
+                         r1q, invq, in0q, bq, in1q, nb, (const int32_t *)nullptr, 1, 0L, 0L);
     } else {
-      family_dispatch(p->family, [&](auto fn, auto fm) {
-        hipLaunchKernelGGL((sipamd::kkt::condense_chain_kernel<false, true, decltype(fn)::value, decltype(fm)::value>),
-                           dim3((unsigned)(nb * p->N)), dim3(sipamd::kkt::TPB), lds_chain, s, ck, mq, r1q, invq, in0q,
-                           (const double *)nullptr, (double *)nullptr, nb);
-      });
+      hipLaunchKernelGGL(p->k->condense, dim3((unsigned)(nb * p->N)), dim3(sipamd::kkt::TPB), lds_chain, s, ck, mq, r1q,
+                         invq, in0q, (const double *)nullptr, (double *)nullptr, nb, (const int32_t *)nullptr, 1, 0L, 0L);
     }
   };
   if (pipe) {
     if (pipe_batch > 0 && b != nullptr)
-      family_dispatch(p->family, [&](auto fn, auto fm) {
-        hipLaunchKernelGGL((sipamd::kkt::condense_chain_pipe_kernel<true, decltype(fn)::value, decltype(fm)::value>),
-                           dim3(pipe_grid), dim3(sipamd::kkt::TPB), lds_chain, s, ck, model, r1, r.inv, r.in0, b,
-                           r.in1, pipe_batch, p->chain_pipe);
-      });
+      hipLaunchKernelGGL(p->k->condense_pipe_rhs, dim3(pipe_grid), dim3(sipamd::kkt::TPB), lds_chain, s, ck, model, r1,
+                         r.inv, r.in0, b, r.in1, pipe_batch, p->chain_pipe);
     else if (pipe_batch > 0)
-      family_dispatch(p->family, [&](auto fn, auto fm) {
-        hipLaunchKernelGGL((sipamd::kkt::condense_chain_pipe_kernel<false, decltype(fn)::value, decltype(fm)::value>),
-                           dim3(pipe_grid), dim3(sipamd::kkt::TPB), lds_chain, s, ck, model, r1, r.inv, r.in0,
-                           (const double *)nullptr, (double *)nullptr, pipe_batch, p->chain_pipe);
-      });
+      hipLaunchKernelGGL(p->k->condense_pipe, dim3(pipe_grid), dim3(sipamd::kkt::TPB), lds_chain, s, ck, model, r1,
+                         r.inv, r.in0, (const double *)nullptr, (double *)nullptr, pipe_batch, p->chain_pipe);
     if (odd_tail)
       one_stage((long)p->batch - 1, 1);
   } else if (p->chain_kernels) { // (SIP_KKT_PIPE=0, or an item longer than one pass of the pipelined walk)
@@ -292,13 +269,10 @@ hipError_t launch_rhs_meta(const sip_kkt_plan *p, const Meta &mt, const Regions 
 hipError_t launch_rhs(const sip_kkt_plan *p, const Regions &r, const double *model, const double *b,
                       const int32_t *status, hipStream_t s) {
   if (p->chain_kernels)
-    family_dispatch(p->family, [&](auto fn, auto fm) {
-      hipLaunchKernelGGL((sipamd::kkt::condense_chain_kernel<true, false, decltype(fn)::value, decltype(fm)::value>),
-                         dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
-                         // (rhs only: the constraint Jacobians | weights | weighted rows)
-                         sizeof(double) * ((size_t)p->ck.lds_tail + 2 * (size_t)p->ck.lds_rows), s, p->ck, model,
-                         (const double *)nullptr, r.inv, r.in0, b, r.in1, (long)p->batch, status);
-    });
+    hipLaunchKernelGGL(p->k->rhs, dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
+                       // (rhs only: the constraint Jacobians | weights | weighted rows)
+                       sizeof(double) * ((size_t)p->ck.lds_tail + 2 * (size_t)p->ck.lds_rows), s, p->ck, model,
+                       (const double *)nullptr, r.inv, r.in0, b, r.in1, (long)p->batch, status, 1, 0L, 0L);
   else if (p->staged)
     hipLaunchKernelGGL(sipamd::kkt::rhs_staged_kernel, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_rhs, s,
                        p->meta, model, b, r.inv, r.in1, status, (long)p->batch);
@@ -311,11 +285,8 @@ hipError_t launch_rhs(const sip_kkt_plan *p, const Regions &r, const double *mod
 hipError_t launch_recover(const sip_kkt_plan *p, const Regions &r, const double *model, const double *b,
                           double *sol, const int32_t *status, hipStream_t s) {
   if (p->chain_kernels)
-    family_dispatch(p->family, [&](auto fn, auto fm) {
-      hipLaunchKernelGGL((sipamd::kkt::recover_chain_kernel<false, decltype(fn)::value, decltype(fm)::value>),
-                         dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_chain_recover, s, p->ck, model, b, r.inv, r.out,
-                         sol, status, (long)p->batch);
-    });
+    hipLaunchKernelGGL(p->k->recover, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_chain_recover, s, p->ck, model,
+                       b, r.inv, r.out, sol, status, (long)p->batch, 1, 0L, 0L, 0L);
   else if (p->staged)
     hipLaunchKernelGGL(sipamd::kkt::recover_staged_kernel, dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
                        p->lds_recover, s, p->meta, model, b, r.inv, r.out, sol, status, (long)p->batch);
@@ -346,11 +317,8 @@ int apply_blocks(const sip_kkt_plan *p, const double *d_model, const double *d_t
     return report(on_device.err, what);
   const int th = d_theta != nullptr ? p->theta_dim : 0;
   if (p->chain_kernels) {
-    family_dispatch(p->family, [&](auto fn, auto fm) {
-      hipLaunchKernelGGL((sipamd::kkt::apply_chain_kernel<decltype(fn)::value, decltype(fm)::value>), dim3(node_grid(p)),
-                         dim3(sipamd::kkt::TPB), p->lds_chain_apply, s, p->ck, th, d_model, d_w, d_r1, d_r2, d_r3, io,
-                         (long)p->batch);
-    });
+    hipLaunchKernelGGL(p->k->apply, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_chain_apply, s, p->ck, th,
+                       d_model, d_w, d_r1, d_r2, d_r3, io, (long)p->batch);
   } else {
     sipamd::kkt::Meta wide = p->meta; // x-space = [stagewise x | theta]
     wide.theta_dim = th;
@@ -364,11 +332,8 @@ int apply_blocks(const sip_kkt_plan *p, const double *d_model, const double *d_t
     const size_t per_wave = sizeof(double) * ((size_t)p->ct.lds_item + vlen + p->ck.lds_rows + 2 * pe);
     int waves = (int)std::min<size_t>(8, (64 * 1024) / per_wave);
     waves = std::max(1, std::min(waves, p->N));
-    family_dispatch(p->family, [&](auto fn, auto fm) {
-      hipLaunchKernelGGL((sipamd::kkt::apply_theta_chain_kernel<decltype(fn)::value, decltype(fm)::value>),
-                         dim3((unsigned)p->batch), dim3(64 * waves), per_wave * waves, s, p->ck, p->ct, d_theta, d_r1, io,
-                         (long)p->batch);
-    });
+    hipLaunchKernelGGL(p->k->apply_theta, dim3((unsigned)p->batch), dim3(64 * waves), per_wave * waves, s, p->ck, p->ct,
+                       d_theta, d_r1, io, (long)p->batch);
   } else if (th > 0)
     hipLaunchKernelGGL(sipamd::kkt::apply_theta_kernel, dim3((unsigned)p->batch), dim3(sipamd::kkt::TPB), 0, s,
                        p->meta, p->theta_meta, d_theta, d_r1, io, (long)p->batch);
@@ -610,12 +575,11 @@ int sip_kkt_plan_create(int64_t batch, int num_edges, int root, const int *edge_
                       (len_last + 1) / 2 <= sipamd::kkt::PIPE_U * sipamd::kkt::TPB;
     p->chain_pipe = fits && per > 0 ? per : 0;
     {
-      const int fn = ck.n, fm = ck.m, fc = std::max(1, fn / 2), fg = std::max(1, 2 * fm);
+      const int fc = sipamd::kkt::family_c(ck.n), fg = sipamd::kkt::family_g(ck.m);
       const char *fe = std::getenv("SIP_KKT_FAMILY");
-      const bool shape = (fn == 4 || fn == 6 || fn == 8 || fn == 12) && fm >= 1 && fm <= 4;
-      if (shape && ck.cn == 0 && ck.gn == 0 && ck.cT == fc && ck.gT == fg && ck.ce == fc && ck.ge == fg &&
+      if (ck.cn == 0 && ck.gn == 0 && ck.cT == fc && ck.gT == fg && ck.ce == fc && ck.ge == fg &&
           !(fe != nullptr && fe[0] == '0'))
-        p->family = 100 * fn + fm;
+        p->k = sipamd::kkt::find_kkt_chain_kernels(ck.n, ck.m);
     }
     const char *se = std::getenv("SIP_KKT_SPLIT");
     p->chain_split = E > 0 && sip_lqr_has_split(p->chain) == 1 && !(se != nullptr && se[0] == '0');
@@ -633,7 +597,7 @@ int sip_kkt_plan_create(int64_t batch, int num_edges, int root, const int *edge_
   p->name += p->chain_kernels ? " + chain condensation" : p->staged ? " + staged condensation" : " + direct condensation";
   if (p->chain_split)
     p->name += p->chain_sym != nullptr ? " (A|B in place, Q|R packed)" : " (A|B in place)";
-  if (p->family > 0)
+  if (p->k->n > 0)
     p->name += " [benchmark-family instantiation]";
 
   std::vector<int> ints;
@@ -1057,22 +1021,17 @@ int sip_kkt_factor_theta(const sip_kkt_plan *p, const double *d_model, const dou
     const Regions r = regions(p, d_work);
     const long colJ = (long)p->batch * skkt, colV = (long)p->batch * p->in1_len;
     double *s_part = t.J;
-    family_dispatch(p->family, [&](auto fn, auto fm) {
-      hipLaunchKernelGGL((sipamd::kkt::theta_rhs_chain_kernel<decltype(fn)::value, decltype(fm)::value>),
-                         dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_theta_rhs, s, p->ck, p->ct, d_model, d_theta,
-                         (const double *)r.inv, t.vecs_cols, colV, (const int32_t *)d_status, (long)p->batch);
-    });
+    hipLaunchKernelGGL(p->k->theta_rhs, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_theta_rhs, s, p->ck, p->ct,
+                       d_model, d_theta, (const double *)r.inv, t.vecs_cols, colV, (const int32_t *)d_status,
+                       (long)p->batch);
     if ((e = hipGetLastError()) != hipSuccess)
       return report(e, "sip_kkt_factor_theta(rhs)");
     rc = sip_lqr_solve_multi(p->chain, r.in0, t.vecs_cols, t.lsol_cols, th, r.gain, r.lqr, t.cws, s);
     if (rc != SIP_LQR_OK)
       return rc;
-    family_dispatch(p->family, [&](auto fn, auto fm) {
-      hipLaunchKernelGGL((sipamd::kkt::theta_recover_chain_kernel<decltype(fn)::value, decltype(fm)::value>),
-                         dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_theta_recover, s, p->ck, p->ct, d_model,
-                         d_theta, (const double *)r.inv, (const double *)t.lsol_cols, colV, t.KJ, colJ, s_part,
-                         (const int32_t *)d_status, (long)p->batch);
-    });
+    hipLaunchKernelGGL(p->k->theta_recover, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_theta_recover, s, p->ck,
+                       p->ct, d_model, d_theta, (const double *)r.inv, (const double *)t.lsol_cols, colV, t.KJ, colJ,
+                       s_part, (const int32_t *)d_status, (long)p->batch);
     if ((e = hipGetLastError()) != hipSuccess)
       return report(e, "sip_kkt_factor_theta(recover)");
     hipLaunchKernelGGL(sipamd::kkt::theta_schur_reduce_kernel, dim3((unsigned)p->batch), dim3(sipamd::kkt::TPB),
@@ -1095,13 +1054,10 @@ int sip_kkt_factor_theta(const sip_kkt_plan *p, const double *d_model, const dou
     const int rhs_cols = 1 + (int)std::min<size_t>((size_t)(th - 1), (64 * 1024 - rhs_lds) / std::max<size_t>(rhs_col_lds, 1));
     for (int c0 = 0; c0 < th; c0 += rhs_cols) {
       const int nc = std::min(rhs_cols, th - c0);
-      family_dispatch(p->family, [&](auto fn, auto fm) {
-        hipLaunchKernelGGL((sipamd::kkt::condense_chain_kernel<true, false, decltype(fn)::value, decltype(fm)::value>),
-                           dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
-                           rhs_lds + rhs_col_lds * (size_t)(nc - 1), s, p->ck, d_model,
-                           (const double *)nullptr, r.inv, r.in0, (const double *)t.J + (size_t)c0 * colJ,
-                           t.vecs_cols + (size_t)c0 * colV, (long)p->batch, (const int32_t *)d_status, nc, colJ, colV);
-      });
+      hipLaunchKernelGGL(p->k->rhs, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), rhs_lds + rhs_col_lds * (size_t)(nc - 1),
+                         s, p->ck, d_model, (const double *)nullptr, r.inv, r.in0,
+                         (const double *)t.J + (size_t)c0 * colJ, t.vecs_cols + (size_t)c0 * colV, (long)p->batch,
+                         (const int32_t *)d_status, nc, colJ, colV);
     }
     if ((e = hipGetLastError()) != hipSuccess)
       return report(e, "sip_kkt_factor_theta(rhs)");
@@ -1115,23 +1071,11 @@ int sip_kkt_factor_theta(const sip_kkt_plan *p, const double *d_model, const dou
     const int rec_cols = 1 + (int)std::min<size_t>((size_t)(th - 1), (64 * 1024 - p->lds_chain_recover) / rec_col_lds);
     for (int c0 = 0; c0 < th; c0 += rec_cols) {
       const int nc = std::min(rec_cols, th - c0);
-      if (nc > 1)
-        family_dispatch(p->family, [&](auto fn, auto fm) {
-          hipLaunchKernelGGL((sipamd::kkt::recover_chain_kernel<true, decltype(fn)::value, decltype(fm)::value>),
-                             dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
-                             p->lds_chain_recover + rec_col_lds * (size_t)(nc - 1), s, p->ck, d_model,
-                             (const double *)t.J + (size_t)c0 * colJ, r.inv,
-                             (const double *)t.lsol_cols + (size_t)c0 * colV, t.KJ + (size_t)c0 * colJ,
-                             (const int32_t *)d_status, (long)p->batch, nc, colJ, colV, colJ);
-        });
-      else
-        family_dispatch(p->family, [&](auto fn, auto fm) {
-          hipLaunchKernelGGL((sipamd::kkt::recover_chain_kernel<false, decltype(fn)::value, decltype(fm)::value>),
-                             dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_chain_recover, s, p->ck, d_model,
-                             (const double *)t.J + (size_t)c0 * colJ, r.inv,
-                             (const double *)t.lsol_cols + (size_t)c0 * colV, t.KJ + (size_t)c0 * colJ,
-                             (const int32_t *)d_status, (long)p->batch, 1, colJ, colV, colJ);
-        });
+      // (nc == 1: lds_chain_recover alone, on the single-column instantiation)
+      hipLaunchKernelGGL(nc > 1 ? p->k->recover_cols : p->k->recover, dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
+                         p->lds_chain_recover + rec_col_lds * (size_t)(nc - 1), s, p->ck, d_model,
+                         (const double *)t.J + (size_t)c0 * colJ, r.inv, (const double *)t.lsol_cols + (size_t)c0 * colV,
+                         t.KJ + (size_t)c0 * colJ, (const int32_t *)d_status, (long)p->batch, nc, colJ, colV, colJ);
     }
     if ((e = hipGetLastError()) != hipSuccess)
       return report(e, "sip_kkt_factor_theta(recover)");
@@ -1201,11 +1145,8 @@ int sip_kkt_solve_theta(const sip_kkt_plan *p, const double *d_model, const doub
     return rc;
   if (p->chain_theta) {
     double *d_part = t.J + (size_t)p->batch * p->N * th * th; // behind the Schur partials (kept: solve after solve)
-    family_dispatch(p->family, [&](auto fn, auto fm) {
-      hipLaunchKernelGGL((sipamd::kkt::theta_dot_chain_kernel<decltype(fn)::value, decltype(fm)::value>),
-                         dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_theta_dot, s, p->ck, p->ct, d_theta,
-                         (const double *)t.sol_sw, d_part, d_status, (long)p->batch);
-    });
+    hipLaunchKernelGGL(p->k->theta_dot, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_theta_dot, s, p->ck, p->ct,
+                       d_theta, (const double *)t.sol_sw, d_part, d_status, (long)p->batch);
     hipLaunchKernelGGL(sipamd::kkt::theta_finish_parts_kernel, dim3((unsigned)p->batch), dim3(sipamd::kkt::TPB),
                        sizeof(double) * (size_t)th, s, p->N, th, sx, skkt, d_b, (const double *)d_part,
                        (const double *)t.KJ, (const double *)t.S, (const double *)t.sol_sw, d_sol, d_status,
@@ -1227,15 +1168,5 @@ int sip_kkt_add_Kx_to_y_theta(const sip_kkt_plan *p, const double *d_model, cons
   return apply_blocks(p, d_model, d_theta, d_w, d_r1, d_r2, d_r3, kkt_vector_io(p, p->theta_dim, d_x, d_y),
                       (hipStream_t)stream, "sip_kkt_add_Kx_to_y_theta");
 }
-
-#ifdef SIP_KKT_STAMPS
-// diagnostic build: read (and clear) the per-segment cycle sums of condense_chain_pipe_kernel
-void sip_kkt_debug_segments(unsigned long long *out16) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out16, HIP_SYMBOL(sipamd::kkt::g_kkt_seg), 16 * sizeof(unsigned long long));
-  unsigned long long zero[16] = {0};
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(sipamd::kkt::g_kkt_seg), zero, sizeof(zero));
-}
-#endif
 
 } // extern "C"

@@ -2,8 +2,8 @@
 
 A uniform chain whose dimensions are those of the reference's NewtonKKTProblem (n in {4, 6, 8, 12}, m in 1..4,
 c = n/2 and g = 2m rows on every edge and on the last node, no interior-node constraints) runs the chain kernels as
-the instantiation with every dimension but the horizon a constant (kkt_chain_kernels.hpp: family_dims, dispatched
-by family_dispatch in sip_kkt_amd.hip): unrolled loops, folded branches and other register caps than the generic
+the instantiation with every dimension but the horizon a constant (kkt_chain_kernels.hpp: family_dims; the plan's row
+of the table of kkt_chain_launch.hpp, instantiated in kkt_chain_kernels.hip): unrolled loops, folded branches and other register caps than the generic
 (FN = 0) kernels, so a bug can live in one (n, m) or one entry point alone.  Here all 16 shapes run every entry
 point -- the step (fused and split, every condensation switch), y += K x, the five block operators and the theta
 Schur complement -- on 1031 distinct problems at T = 13 (1031 x 14 stages is not a multiple of the 6 stages per

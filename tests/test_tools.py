@@ -60,11 +60,10 @@ def test_flags_trans_result_used_by_next_valu():
     assert _probs(f"{rcp}\n\tv_fma_f64 v[8:9], v[12:13], v[6:7], v[10:11]") == []     # unrelated registers
 
 
-def test_shipped_kernels_are_hazard_free():
-    """Every fused chain kernel of the library as built (the build keeps the device assembly of each
-    translation unit: __graft_entry__.build_hip) passes the hazard checker."""
+def _shipped_listings():
+    """The device assembly of every translation unit of the library as built (the build keeps it next to each
+    object: __graft_entry__.build_hip), by unit name."""
     import glob
-    import subprocess
     import sys
     if not os.path.exists("/opt/rocm/bin/hipcc"):
         import pytest
@@ -73,10 +72,17 @@ def test_shipped_kernels_are_hazard_free():
     import __graft_entry__ as entry
     pattern = os.path.join(ROOT, "build", "obj", "*", "*-hip-amdgcn-amd-amdhsa-gfx950.s")
     entry.build_hip()
-    if len(glob.glob(pattern)) < 5 + entry.QW16_SLICES or not entry.listings_current():
+    if len(glob.glob(pattern)) < len(entry.hip_units()) or not entry.listings_current():
         entry.build_hip(force=True)  # library from elsewhere (no build/obj): rebuild with listings
-    listings = sorted(glob.glob(pattern))
-    units = {os.path.basename(os.path.dirname(p)) for p in listings}
+    return entry, {os.path.basename(os.path.dirname(p)): p for p in sorted(glob.glob(pattern))}
+
+
+def test_shipped_kernels_are_hazard_free():
+    """Every fused chain kernel of the library as built passes the hazard checker."""
+    import subprocess
+    import sys
+    entry, by_unit = _shipped_listings()
+    listings, units = list(by_unit.values()), set(by_unit)
     assert {"sip_lqr_amd", "tree_qw16"} | {"qw16_kernels_%d" % k for k in range(entry.QW16_SLICES)} <= units
     checked = 0
     for path in listings:
@@ -101,6 +107,24 @@ def test_shipped_kernels_are_hazard_free():
             staged += 1
             assert re.search(r"\.amdhsa_private_segment_fixed_size 0\b", m.group(2)), m.group(1) + " uses scratch"
     assert staged >= 10
+
+
+def test_newton_kkt_chain_kernels_live_in_their_own_units():
+    """Every instantiation of the Newton-KKT chain kernels (12 templates x (16 family shapes + the generic one)) is
+    defined once, in a unit of kkt_chain_kernels.hip; sip_kkt_amd.hip, which launches them through the table of
+    kkt_chain_launch.hpp, instantiates none (one that crept back in would bring the long compile of that unit back
+    without failing anything else)."""
+    import re
+    entry, by_unit = _shipped_listings()
+
+    def chain_kernels(unit):
+        return re.findall(r"^\s*\.amdhsa_kernel (\S*(?:chain_kernel|chain_pipe_kernel)\S*)", open(by_unit[unit]).read(), re.M)
+
+    assert chain_kernels("sip_kkt_amd") == []
+    chain_units = sorted(u for u in by_unit if u.startswith("kkt_chain_kernels_"))
+    assert chain_units == sorted("kkt_chain_kernels_%d" % n for n in entry.KKT_CHAIN_SLICES)
+    defined = [k for u in chain_units for k in chain_kernels(u)]
+    assert len(defined) == 204 and len(set(defined)) == 204
 
 
 def _wait_probs(text):
