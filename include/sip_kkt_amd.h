@@ -291,6 +291,62 @@ int sip_kkt_add_GTx_to_y_theta(const sip_kkt_plan *plan, const double *d_model,
                                const double *d_theta_model, const double *d_x,
                                double *d_y, void *stream);
 
+/* ------------------------------------------------------------------------
+ * First-order model outputs: f, grad f, c, g on the device.
+ *
+ * Replaces what the reference's model_callback wrapper assembles after every
+ * model evaluation (sip_optimal_control.cpp:47-125) and get_f / get_grad_f /
+ * get_c / get_g hand to SIP (:172-180): with the eight operators above, all
+ * twelve callbacks of sip::Input are then served from device memory.
+ *
+ * first-order arena [sip_kkt_first_order_len(plan)] per problem (doubles,
+ * compact, node i followed by edge i; the first-order fields of
+ * NodeModelCallbackOutput / EdgeModelCallbackOutput in the order of
+ * types.hpp:48-89):
+ *   node i : f (1) | df_dx (n_i) | df_dtheta (p) | c (c_i) | g (g_i)
+ *   edge e : f (1) | df_dx (np) | df_du (m) | df_dtheta (p) | dyn_res (nc) |
+ *            c (ce) | g (ge)
+ * p is the plan's theta_dim: 0 until sip_kkt_plan_set_theta, so the length
+ * and the offsets are to be read AFTER that call (it rebuilds and uploads
+ * the table).  Zero dimensions give empty blocks; blocks are 8-byte aligned
+ * only.
+ * ---------------------------------------------------------------------- */
+enum {
+  SIP_KKT_FO_NODE_F = 0, SIP_KKT_FO_NODE_DF_DX, SIP_KKT_FO_NODE_DF_DTHETA, SIP_KKT_FO_NODE_C, SIP_KKT_FO_NODE_G,
+  SIP_KKT_FO_EDGE_F, SIP_KKT_FO_EDGE_DF_DX, SIP_KKT_FO_EDGE_DF_DU, SIP_KKT_FO_EDGE_DF_DTHETA,
+  SIP_KKT_FO_EDGE_DYN_RES, SIP_KKT_FO_EDGE_C, SIP_KKT_FO_EDGE_G, SIP_KKT_FO_NUM_BLOCKS
+};
+/* 0 for a NULL or invalid plan */
+size_t sip_kkt_first_order_len(const sip_kkt_plan *plan);
+/* (size_t)-1 for a NULL or invalid plan or an out-of-range request */
+size_t sip_kkt_first_order_offset(const sip_kkt_plan *plan, int block, int index);
+
+/* d_first [batch][sip_kkt_first_order_len]; d_x [batch][x_dim + p], SIP's
+ * primal vector, of which only the root state (at SIP_KKT_X_STATE[root]) is
+ * read; d_initial_state [batch][n_root].  Outputs are overwritten:
+ *   d_f [batch]: node terms 0..N-1, then edge terms 0..E-1, added in that
+ *     order (:47-53);
+ *   d_grad_f [batch][x_dim + p]: state rows of node v = its df_dx, then the
+ *     df_dx of every edge whose parent is v in increasing edge index; control
+ *     rows of edge e = its df_du; theta rows = df_dtheta of nodes 0..N-1, then
+ *     of edges 0..E-1 (:56-88);
+ *   d_c [batch][y_dim]: dyn rows of the root = initial_state - x_root, dyn
+ *     rows of every edge's child = its dyn_res, node c and edge c copied
+ *     (:90-112);
+ *   d_g [batch][z_dim]: node g and edge g copied (:114-125).
+ * Every entry is produced by one lane that adds its terms in the reference's
+ * order: the results are bit-identical to the reference's loops.
+ * d_grad_f, d_c and d_g may ALL be NULL: only f is written (mci.new_x ==
+ * false, :55), d_x and d_initial_state are then not read.  Otherwise each of
+ * them whose space is not empty is required.  SIP_LQR_ERR_INVALID_ARGUMENT,
+ * before any HIP call: NULL plan, a plan whose sip_kkt_input_status != 0, a
+ * missing required pointer, any other mix of NULL and non-NULL outputs.
+ * Asynchronous on `stream`, kernels only. */
+int sip_kkt_gather_first_order(const sip_kkt_plan *plan, const double *d_first,
+                               const double *d_x, const double *d_initial_state,
+                               double *d_f, double *d_grad_f, double *d_c, double *d_g,
+                               void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,9 @@ _SIGNATURES = {
     "sip_kkt_factor_theta": (ctypes.c_int, [_P] * 11),
     "sip_kkt_solve_theta": (ctypes.c_int, [_P] * 9),
     "sip_kkt_add_Kx_to_y_theta": (ctypes.c_int, [_P] * 10),
+    "sip_kkt_first_order_len": (ctypes.c_size_t, [_P]),
+    "sip_kkt_first_order_offset": (ctypes.c_size_t, [_P, ctypes.c_int, ctypes.c_int]),
+    "sip_kkt_gather_first_order": (ctypes.c_int, [_P] * 9),
 }
 for _op in ("Hx", "Cx", "CTx", "Gx", "GTx"):  # the five block operators, helpers.hpp:20-24
     _SIGNATURES[f"sip_kkt_add_{_op}_to_y"] = (ctypes.c_int, [_P] * 5)

@@ -16,6 +16,7 @@
 #include "generic_plan.hpp"
 #include "stream_fill.hpp"
 #include "kkt_chain_launch.hpp"
+#include "kkt_first_order_kernels.hpp"
 
 const sipamd::kkt::KktChainKernels *sipamd::kkt::find_kkt_chain_kernels(const int n, const int m) {
 #define SIP_KKT_ROW_IF(N, M) \
@@ -79,6 +80,13 @@ struct sip_kkt_plan {
   size_t at_tree_scratch = 0;
   sipamd::kkt::ChainTheta ct{};
   size_t lds_theta_rhs = 0, lds_theta_recover = 0, lds_theta_dot = 0;
+  // first-order arena (sip_kkt_gather_first_order): block offsets, their copy at fo_at of d_longs -- uploaded by
+  // sip_kkt_plan_create and again by sip_kkt_plan_set_theta (df_dtheta then has theta_dim entries), never at first use
+  std::vector<long> foff[sipamd::kkt::FO_NUM_BLOCKS];
+  long first_len = 0;
+  size_t fo_at = 0;
+  bool fo_uniform = false; // chain_kernels plans: gather_first_order_uniform (arithmetic offsets)
+  sipamd::kkt::FoUniform fu{};
   bool staged = false; // LDS-staged kernels (false: items too large for LDS, or SIP_KKT_VARIANT=direct)
   size_t lds_condense = 0, lds_rhs = 0, lds_recover = 0;
   std::string name;
@@ -139,6 +147,78 @@ bool is_uniform_chain(const sip_kkt_plan &p) {
 }
 
 size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+
+// The first-order arena for theta_dim = th (types.hpp:48-89, first-order fields): node i, then edge i.
+long first_order_layout(const sip_kkt_plan &p, const int th, std::vector<long> (&off)[sipamd::kkt::FO_NUM_BLOCKS]) {
+  using namespace sipamd::kkt;
+  for (auto &v : off)
+    v.assign(p.N, 0);
+  long at = 0;
+  for (int i = 0; i < p.N; ++i) {
+    off[FO_N_F][i] = at, at += 1;
+    off[FO_N_DX][i] = at, at += p.sd[i];
+    off[FO_N_DTH][i] = at, at += th;
+    off[FO_N_C][i] = at, at += p.ncd[i];
+    off[FO_N_G][i] = at, at += p.ngd[i];
+    if (i < p.E) {
+      const int e = i;
+      off[FO_E_F][e] = at, at += 1;
+      off[FO_E_DX][e] = at, at += p.sd[p.parents[e]];
+      off[FO_E_DU][e] = at, at += p.cd[e];
+      off[FO_E_DTH][e] = at, at += th;
+      off[FO_E_DYN][e] = at, at += p.sd[p.children[e]];
+      off[FO_E_C][e] = at, at += p.ecd[e];
+      off[FO_E_G][e] = at, at += p.egd[e];
+    }
+  }
+  return at;
+}
+
+std::vector<long> first_order_table(const std::vector<long> (&off)[sipamd::kkt::FO_NUM_BLOCKS]) {
+  std::vector<long> flat;
+  for (const auto &v : off)
+    flat.insert(flat.end(), v.begin(), v.end());
+  return flat;
+}
+
+// Takes over a layout (and the theta_dim it was made for) once its table is on the device.  Chain plans get the
+// arithmetic form of it, checked here against the table block by block.
+void first_order_commit(sip_kkt_plan *p, const int th, std::vector<long> (&off)[sipamd::kkt::FO_NUM_BLOCKS],
+                        const long len) {
+  using namespace sipamd::kkt;
+  for (int b = 0; b < FO_NUM_BLOCKS; ++b)
+    p->foff[b].swap(off[b]);
+  p->first_len = len;
+  p->fo_uniform = false;
+  if (!p->chain_kernels)
+    return;
+  const ChainKkt &ck = p->ck;
+  FoUniform &fu = p->fu;
+  fu.n = ck.n, fu.m = ck.m, fu.T = ck.T, fu.p = th;
+  fu.cn = ck.cn, fu.gn = ck.gn, fu.cT = ck.cT, fu.gT = ck.gT, fu.ce = ck.ce, fu.ge = ck.ge;
+  fu.node_len = 1 + fu.n + th + fu.cn + fu.gn;
+  fu.edge_len = 1 + 2 * fu.n + fu.m + th + fu.ce + fu.ge;
+  fu.x_dim = p->x_dim, fu.y_dim = p->y_dim, fu.z_dim = p->z_dim, fu.len = len;
+  bool same = len == (long)fu.T * (fu.node_len + fu.edge_len) + 1 + fu.n + th + fu.cT + fu.gT && p->root == 0;
+  for (int i = 0; i < p->N && same; ++i) {
+    const long base = (long)i * (fu.node_len + fu.edge_len), edge = base + fu.node_len;
+    const int c = i == p->E ? fu.cT : fu.cn;
+    same = p->foff[FO_N_F][i] == base && p->foff[FO_N_DX][i] == base + 1 && p->foff[FO_N_DTH][i] == base + 1 + fu.n &&
+           p->foff[FO_N_C][i] == base + 1 + fu.n + th && p->foff[FO_N_G][i] == base + 1 + fu.n + th + c &&
+           p->voff[SIP_KKT_X_STATE][i] == i * (fu.n + fu.m) && p->voff[SIP_KKT_Y_DYN][i] == i * (fu.n + fu.cn) &&
+           p->voff[SIP_KKT_Y_NODE_C][i] == i * (fu.n + fu.cn) + fu.n && p->voff[SIP_KKT_Z_NODE][i] == i * fu.gn;
+    if (same && i < p->E)
+      same = p->foff[FO_E_F][i] == edge && p->foff[FO_E_DX][i] == edge + 1 && p->foff[FO_E_DU][i] == edge + 1 + fu.n &&
+             p->foff[FO_E_DTH][i] == edge + 1 + fu.n + fu.m && p->foff[FO_E_DYN][i] == edge + 1 + fu.n + fu.m + th &&
+             p->foff[FO_E_C][i] == edge + 1 + 2 * fu.n + fu.m + th &&
+             p->foff[FO_E_G][i] == edge + 1 + 2 * fu.n + fu.m + th + fu.ce &&
+             p->voff[SIP_KKT_X_CONTROL][i] == i * (fu.n + fu.m) + fu.n &&
+             p->voff[SIP_KKT_Y_EDGE_C][i] == p->N * fu.n + fu.T * fu.cn + fu.cT + i * fu.ce &&
+             p->voff[SIP_KKT_Z_EDGE][i] == fu.T * fu.gn + fu.gT + i * fu.ge && p->parents[i] == i &&
+             p->children[i] == i + 1;
+  }
+  p->fo_uniform = same;
+}
 
 int report(hipError_t e, const char *what) {
   if (e == hipSuccess)
@@ -625,6 +705,9 @@ int sip_kkt_plan_create(int64_t batch, int num_edges, int root, const int *edge_
   size_t a_l[12];
   for (int t = 0; t < 12; ++t)
     a_l[t] = pl(*lq[t]);
+  std::vector<long> fo_layout[FO_NUM_BLOCKS];
+  const long fo_len = first_order_layout(*p, 0, fo_layout);
+  p->fo_at = pl(first_order_table(fo_layout));
 
   sipamd::DeviceGuard on_device(device); // the caller's current device is restored on return
   hipError_t he = on_device.err;
@@ -658,6 +741,7 @@ int sip_kkt_plan_create(int64_t batch, int num_edges, int root, const int *edge_
   const long **dst[12] = {&m.oQ, &m.od, &m.oq, &m.oc, &m.ox, &m.oy, &m.oA, &m.oB, &m.oM, &m.oR, &m.orr, &m.ou};
   for (int t = 0; t < 12; ++t)
     *dst[t] = dl + a_l[t];
+  first_order_commit(p, 0, fo_layout, fo_len);
   p->input_status = SIP_KKT_SUCCESS;
   return SIP_LQR_OK;
 }
@@ -845,6 +929,57 @@ SIP_KKT_BLOCK_OP(Gx, AP_G, 0, 2)
 SIP_KKT_BLOCK_OP(GTx, AP_GT, 2, 0)
 #undef SIP_KKT_BLOCK_OP
 
+size_t sip_kkt_first_order_len(const sip_kkt_plan *p) {
+  return (p && p->input_status == SIP_KKT_SUCCESS) ? (size_t)p->first_len : 0;
+}
+
+size_t sip_kkt_first_order_offset(const sip_kkt_plan *p, int block, int index) {
+  if (p == nullptr || p->input_status != SIP_KKT_SUCCESS || block < 0 || block >= SIP_KKT_FO_NUM_BLOCKS ||
+      index < 0 || index >= (block <= SIP_KKT_FO_NODE_G ? p->N : p->E))
+    return (size_t)-1;
+  return (size_t)p->foff[block][index];
+}
+
+// Replaces the assembly of f, gradient_f, c and g in the reference's model_callback wrapper
+// (sip_optimal_control.cpp:47-125); kkt_first_order_kernels.hpp.
+int sip_kkt_gather_first_order(const sip_kkt_plan *p, const double *d_first, const double *d_x,
+                               const double *d_initial_state, double *d_f, double *d_grad_f, double *d_c,
+                               double *d_g, void *stream) {
+  if (p == nullptr || p->input_status != SIP_KKT_SUCCESS || d_first == nullptr || d_f == nullptr)
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  const long xt = (long)p->x_dim + p->theta_dim;
+  const bool f_only = d_grad_f == nullptr && d_c == nullptr && d_g == nullptr; // mci.new_x == false, :55
+  if (!f_only) {
+    if ((!d_grad_f && xt > 0) || (!d_c && p->y_dim > 0) || (!d_g && p->z_dim > 0))
+      return SIP_LQR_ERR_INVALID_ARGUMENT;
+    if (p->sd[p->root] > 0 && (d_x == nullptr || d_initial_state == nullptr))
+      return SIP_LQR_ERR_INVALID_ARGUMENT;
+  }
+  sipamd::DeviceGuard on_device(p->device); // launch on the plan's device, whatever the caller's current one
+  if (on_device.err != hipSuccess)
+    return report(on_device.err, "sip_kkt_gather_first_order(hipSetDevice)");
+  using namespace sipamd::kkt;
+  hipStream_t s = (hipStream_t)stream;
+  const FoTables ft{(const long *)p->d_longs + p->fo_at, p->first_len, p->theta_dim};
+  if (!f_only && p->fo_uniform)
+    hipLaunchKernelGGL(gather_first_order_uniform, dim3((unsigned)((p->batch * p->N + FO_WAVES - 1) / FO_WAVES)),
+                       dim3(FO_TPB), 0, s, p->fu, d_first, d_x, d_initial_state, d_grad_f, d_c, d_g, (long)p->batch);
+  else if (!f_only)
+    hipLaunchKernelGGL(gather_first_order_tree,
+                       dim3((unsigned)((p->batch * (p->N + p->E) + FO_WAVES - 1) / FO_WAVES)), dim3(FO_TPB), 0, s,
+                       p->meta, ft, d_first, d_x, d_initial_state, d_grad_f, d_c, d_g, (long)p->batch);
+  // f and the theta rows: after the pass above, which has just read the same lines
+  const int comps = f_only ? 1 : 1 + p->theta_dim;
+  const dim3 grid((unsigned)((p->batch * comps + FO_TPB - 1) / FO_TPB));
+  if (p->fo_uniform)
+    hipLaunchKernelGGL(gather_first_order_sums<true>, grid, dim3(FO_TPB), 0, s, p->fu, ft, p->N, p->x_dim, comps,
+                       d_first, d_f, d_grad_f, (long)p->batch);
+  else
+    hipLaunchKernelGGL(gather_first_order_sums<false>, grid, dim3(FO_TPB), 0, s, p->fu, ft, p->N, p->x_dim, comps,
+                       d_first, d_f, d_grad_f, (long)p->batch);
+  return report(hipGetLastError(), "sip_kkt_gather_first_order");
+}
+
 } // extern "C"
 
 // ---------------------------------------------------------------------------
@@ -921,8 +1056,16 @@ int sip_kkt_plan_set_theta(sip_kkt_plan *p, int theta_dim) {
     he = hipMalloc(&p->d_theta_longs, longs.size() * sizeof(long));
   if (he == hipSuccess)
     he = hipMemcpy(p->d_theta_longs, longs.data(), longs.size() * sizeof(long), hipMemcpyHostToDevice);
+  // the first-order arena carries df_dtheta (th entries per node and edge): its table again, now, not at first use
+  std::vector<long> fo_layout[FO_NUM_BLOCKS];
+  const long fo_len = first_order_layout(*p, th, fo_layout);
+  if (he == hipSuccess) {
+    const std::vector<long> flat = first_order_table(fo_layout);
+    he = hipMemcpy((long *)p->d_longs + p->fo_at, flat.data(), flat.size() * sizeof(long), hipMemcpyHostToDevice);
+  }
   if (he != hipSuccess)
     return report(he, "sip_kkt_plan_set_theta");
+  first_order_commit(p, th, fo_layout, fo_len);
   p->theta_len = at, p->theta_dim = th;
   p->theta_meta.p = th, p->theta_meta.theta_len = at;
   if (p->chain_kernels && E >= 1) {

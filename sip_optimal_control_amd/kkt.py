@@ -17,6 +17,9 @@ from .chain import _check
 
 NODE_BLOCKS = ("d2L_dx2", "dc_dx", "dg_dx")
 EDGE_BLOCKS = ("d2L_dx2", "d2L_dxdu", "d2L_du2", "ddyn_dx", "ddyn_du", "dc_dx", "dc_du", "dg_dx", "dg_du")
+# blocks of the first-order arena (SIP_KKT_FO_*): node blocks, then edge blocks
+FIRST_ORDER_NODE_BLOCKS = ("f", "df_dx", "df_dtheta", "c", "g")
+FIRST_ORDER_EDGE_BLOCKS = ("f", "df_dx", "df_du", "df_dtheta", "dyn_res", "c", "g")
 VECTOR_TABLES = ("x_state", "x_control", "y_dyn", "y_node_c", "y_edge_c", "z_node", "z_edge")
 STATUS_NONPOSITIVE_REGULARIZATION = 5
 STATUS_INVALID_INPUT = 6
@@ -35,6 +38,7 @@ class BatchedNewtonKKT:
         self._lib = load_library()
         self.device = resolve_device(device)  # explicit ordinal; raises without a HIP device
         self.E, self.N, self.batch = len(control_dims), len(control_dims) + 1, int(batch)
+        self.root_state_dim = int(state_dims[root]) if 0 <= root < len(state_dims) else 0
         h = ctypes.c_void_p()
         _check(self._lib.sip_kkt_plan_create(self.batch, self.E, root, _ints(parents), _ints(children),
                                              _ints(state_dims), _ints(control_dims), _ints(node_c_dims),
@@ -57,6 +61,7 @@ class BatchedNewtonKKT:
             self.theta_work = torch.empty(max(1, self._lib.sip_kkt_theta_work_bytes(h)), dtype=torch.uint8,
                                           device=self.device)
         self.full_dim = self.kkt_dim + self.theta_dim
+        self.first_order_len = self._lib.sip_kkt_first_order_len(h)  # (after set_theta: df_dtheta has theta_dim rows)
         self.status = torch.full((self.batch,), -1, dtype=torch.int32, device=self.device)
 
     def model_offset(self, block, index):
@@ -140,6 +145,36 @@ class BatchedNewtonKKT:
             _check(fn(self._plan, self._ptr(model, self.model_len), xs, ys, self._stream()),
                    f"sip_kkt_add_{name}_to_y")
         return y
+
+    # ---- f, grad f, c, g from the first-order model outputs (sip_optimal_control.cpp:47-125) ----
+    def first_order_offset(self, block, index):
+        off = self._lib.sip_kkt_first_order_offset(self._plan, block, index)
+        if off == ctypes.c_size_t(-1).value:
+            raise IndexError((block, index))
+        return off
+
+    def gather_first_order(self, first, x, initial_state, f=None, grad_f=None, c=None, g=None, new_x=True):
+        """(f, grad_f, c, g) of every problem from `first` [batch, first_order_len]; x is [batch, x_dim + theta_dim]
+        (its root state is read), initial_state [batch, n_root].  Outputs are overwritten.  new_x=False: only f
+        (x and initial_state are not read), returns (f, None, None, None)."""
+        xt = self.x_dim + self.theta_dim
+        if f is None:
+            f = torch.zeros(self.batch, dtype=torch.float64, device=self.device)
+        if new_x:
+            if grad_f is None:
+                grad_f = torch.zeros(self.batch, xt, dtype=torch.float64, device=self.device)
+            if c is None:
+                c = torch.zeros(self.batch, self.y_dim, dtype=torch.float64, device=self.device)
+            if g is None:
+                g = torch.zeros(self.batch, self.z_dim, dtype=torch.float64, device=self.device)
+            ptrs = (self._ptr(x, xt), self._ptr(initial_state, self.root_state_dim), self._ptr(f, 1),
+                    self._ptr(grad_f, xt), self._ptr(c, self.y_dim), self._ptr(g, self.z_dim))
+        else:
+            grad_f = c = g = None
+            ptrs = (None, None, self._ptr(f, 1), None, None, None)
+        _check(self._lib.sip_kkt_gather_first_order(self._plan, self._ptr(first, self.first_order_len), *ptrs,
+                                                    self._stream()), "sip_kkt_gather_first_order")
+        return f, grad_f, c, g
 
     # ---- theta_dim > 0: r1 is [batch, x_dim + p], b / sol / x / y are [batch, full_dim] ----
     def theta_offset(self, block, index):
