@@ -52,21 +52,47 @@ typedef double d2_t __attribute__((ext_vector_type(2)));
 constexpr __host__ __device__ int family_c(const int n) { return n / 2 > 0 ? n / 2 : 1; }
 constexpr __host__ __device__ int family_g(const int m) { return 2 * m > 0 ? 2 * m : 1; }
 
+constexpr int LDS_DOUBLES = 64 * 1024 / (int)sizeof(double); // of a workgroup
+// How many columns or wavefronts (at most `want`, at least one) LDS holds of a partition that grows with their count:
+// `one` is the description for a count of one, and each further one adds `one.each` doubles.  One that alone exceeds
+// LDS gives 1 (no plan gets there: the 48 / 64 KiB eligibility of the plan is decided on larger partitions).
+template <class L>
+constexpr int lds_count_that_fits(const L &one, const int want) {
+  const long more = one.total() < LDS_DOUBLES ? (LDS_DOUBLES - one.total()) / (one.each > 0 ? one.each : 1) : 0;
+  return 1 + (int)(want - 1 < more ? want - 1 : more);
+}
+
+// LDS regions start on even doubles: 16-byte pieces
+constexpr __host__ __device__ __forceinline__ int even(const int v) { return (v + 1) & ~1; }
+
+// The fields of a ChainKkt that follow from its dimensions (n, m, cn, gn, cT, gT, ce, ge) and layout (split, sym): the
+// item lengths, the stage strides and the LDS plan.  The one derivation: the host's plan, its split / packed variant
+// at launch and the family instantiations on the device (where, the dimensions being constants, it folds away).
+// The lengths of whole arenas (model_len, x / y / z_dim, mats_len, vecs_len) are the plan's and travel as they are.
+constexpr __host__ __device__ __forceinline__ ChainKkt chain_kkt_derive(ChainKkt ck) {
+  const int n = ck.n, m = ck.m;
+  ck.node_len = n * n + (ck.cn + ck.gn) * n;
+  ck.edge_len = 2 * n * n + 2 * n * m + m * m + (ck.ce + ck.ge) * (n + m);
+  ck.vecs_stage = 2 * n + m;
+  const int qlen = ck.sym ? n * (n + 1) / 2 : n * n, rlen = ck.sym ? m * (m + 1) / 2 : m * m;
+  ck.mats_stage = ck.split ? (qlen + n) + (n * m + rlen) : (n * n + n) + (n * n + 2 * n * m + m * m);
+  const int cgn = ck.cn + ck.gn > ck.cT + ck.gT ? ck.cn + ck.gn : ck.cT + ck.gT, cge = ck.ce + ck.ge;
+  ck.lds_item = even(n * n + cgn * n + ck.edge_len);
+  ck.lds_tail = even(cgn * n + cge * (n + m)); // recover: every Jacobian of a stage
+  ck.lds_rows = even(cgn + cge);               // condense: weights | weighted rhs rows
+  return ck;
+}
+// doubles of a problem's mats in the layout of `ck`: T stage blocks and the terminal node's [Q_mod | dyn_r2]
+constexpr __host__ __device__ long chain_mats_len(const ChainKkt &ck) {
+  return (long)ck.T * ck.mats_stage + (ck.sym ? ck.n * (ck.n + 1) / 2 : ck.n * ck.n) + ck.n;
+}
+
 template <int FN, int FM>
-__device__ __forceinline__ ChainKkt family_dims(ChainKkt ck) {
+constexpr __host__ __device__ __forceinline__ ChainKkt family_dims(ChainKkt ck) {
   if constexpr (FN > 0) {
     constexpr int c = family_c(FN), g = family_g(FM);
-    constexpr int n = FN, m = FM;
-    ck.n = n, ck.m = m, ck.cn = 0, ck.gn = 0, ck.cT = c, ck.gT = g, ck.ce = c, ck.ge = g;
-    ck.node_len = n * n;
-    ck.edge_len = 2 * n * n + 2 * n * m + m * m + (c + g) * (n + m);
-    ck.vecs_stage = 2 * n + m;
-    const int qlen = ck.sym ? n * (n + 1) / 2 : n * n, rlen = ck.sym ? m * (m + 1) / 2 : m * m;
-    ck.mats_stage = ck.split ? (qlen + n) + (n * m + rlen) : (n * n + n) + (n * n + 2 * n * m + m * m);
-    constexpr int cgn = c + g, cge = c + g;
-    ck.lds_item = (n * n + cgn * n + ck.edge_len + 1) / 2 * 2;
-    ck.lds_tail = (cgn * n + cge * (n + m) + 1) / 2 * 2;
-    ck.lds_rows = (cgn + cge + 1) / 2 * 2;
+    ck.n = FN, ck.m = FM, ck.cn = 0, ck.gn = 0, ck.cT = c, ck.gT = g, ck.ce = c, ck.ge = g;
+    ck = chain_kkt_derive(ck);
   }
   return ck;
 }
@@ -505,6 +531,26 @@ __device__ __forceinline__ void condense_compute(const ChainKkt &ck, const Conde
 #ifndef SIP_KKT_RHS_WAVES
 #define SIP_KKT_RHS_WAVES 8
 #endif
+// LDS of the condensation (one-stage and pipelined).  mats: stage image (lds_item) | weights | weighted rhs rows | r1 of
+// the stage | the stage block of mats on its way out -- of THIS layout (split / packed blocks are smaller: more
+// workgroups per CU).  Right-hand sides only: the constraint Jacobians of the stage (lds_tail) | weights | one block of
+// weighted rows per column.
+struct CondenseLds {
+  int buf, wl;
+  long wr;
+  int r1s, obuf; // (there with mats only)
+  bool mats;
+  int each; // doubles a further column adds
+  constexpr __host__ __device__ long total() const { return buf + wl + wr + (mats ? r1s + obuf : 0); }
+};
+constexpr __host__ __device__ __forceinline__ CondenseLds condense_lds(const ChainKkt &ck, const bool mats,
+                                                                       const int ncols) {
+  CondenseLds l{};
+  l.buf = mats ? ck.lds_item : ck.lds_tail, l.wl = ck.lds_rows;
+  l.wr = (long)(mats || ncols < 1 ? 1 : ncols) * ck.lds_rows, l.each = mats ? 0 : ck.lds_rows;
+  l.r1s = even(ck.n + ck.m), l.obuf = ck.mats_stage, l.mats = mats;
+  return l;
+}
 template <bool WITH_RHS, bool MATS = true, int FN = 0, int FM = 0>
 __global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(FN > 0 && !MATS ? SIP_KKT_RHS_WAVES : 1, 8)))
 condense_chain_kernel(const ChainKkt ck_in, const double *__restrict__ model_all, const double *__restrict__ r1_all,
@@ -518,10 +564,9 @@ condense_chain_kernel(const ChainKkt ck_in, const double *__restrict__ model_all
   static_assert(MATS || WITH_RHS, "nothing to do");
   const ChainKkt ck = family_dims<FN, FM>(ck_in);
   extern __shared__ double sm[];
-  // wr: one block of lds_rows per right-hand-side column when there are several (MATS = false)
-  double *buf = sm, *wl = buf + (MATS ? ck.lds_item : ck.lds_tail), *wr = wl + ck.lds_rows,
-         *r1s = wr + (long)(MATS || ncols < 1 ? 1 : ncols) * ck.lds_rows;
-  double *obuf = r1s + ((ck.n + ck.m + 1) & ~1); // MATS: the stage block of mats before it leaves
+  const CondenseLds lds = condense_lds(ck, MATS, ncols);
+  // (r1s, obuf: regions of the MATS layout only -- without MATS they point past the allocation and are not used)
+  double *buf = sm, *wl = buf + lds.buf, *wr = wl + lds.wl, *r1s = wr + lds.wr, *obuf = r1s + lds.r1s;
   const long p = blockIdx.x / (ck.T + 1);
   const int i = blockIdx.x - (unsigned)(p * (ck.T + 1));
   if (p >= batch || (!MATS && status != nullptr && status[p] != 0))
@@ -585,8 +630,8 @@ condense_chain_pipe_kernel(const ChainKkt ck_in, const double *__restrict__ mode
                            double *__restrict__ vecs_all, const long batch, const int per_block) {
   const ChainKkt ck = family_dims<FN, FM>(ck_in);
   extern __shared__ double sm[];
-  double *buf = sm, *wl = buf + ck.lds_item, *wr = wl + ck.lds_rows, *r1s = wr + ck.lds_rows;
-  double *obuf = r1s + ((ck.n + ck.m + 1) & ~1);
+  const CondenseLds lds = condense_lds(ck, true, 1);
+  double *buf = sm, *wl = buf + lds.buf, *wr = wl + lds.wl, *r1s = wr + lds.wr, *obuf = r1s + lds.r1s;
   const int tid = threadIdx.x;
   const long total = batch * (ck.T + 1);
   const long first = (long)blockIdx.x * per_block;
@@ -675,6 +720,17 @@ condense_chain_pipe_kernel(const ChainKkt ck_in, const double *__restrict__ mode
 #ifndef SIP_KKT_RECOVER_WAVES
 #define SIP_KKT_RECOVER_WAVES 8
 #endif
+// LDS: the constraint Jacobians of the stage, node's then edge's, packed (lds_tail) | x_i | u_i of every column
+struct RecoverLds {
+  int jn, xs;
+  int each; // doubles a further column adds
+  constexpr __host__ __device__ int total() const { return jn + xs; }
+};
+constexpr __host__ __device__ __forceinline__ RecoverLds recover_lds(const ChainKkt &ck, const int ncols) {
+  RecoverLds l{};
+  l.jn = ck.lds_tail, l.each = ck.n + ck.m, l.xs = (ncols < 1 ? 1 : ncols) * l.each;
+  return l;
+}
 template <bool COLS = false, int FN = 0, int FM = 0>
 __global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(FN > 0 && !COLS ? SIP_KKT_RECOVER_WAVES : 1, 8)))
 recover_chain_kernel(const ChainKkt ck_in, const double *__restrict__ model_all, const double *__restrict__ b_all,
@@ -699,7 +755,8 @@ recover_chain_kernel(const ChainKkt ck_in, const double *__restrict__ model_all,
   const double *yinv = inv_all + p * ((long)ck.y_dim + ck.z_dim), *zinv = yinv + ck.y_dim;
   const int y_dyn = i * (n + ck.cn), y_nc = y_dyn + n, y_ec = T * (n + ck.cn) + n + ck.cT + i * ck.ce;
   const int z_n = i * ck.gn, z_e = T * ck.gn + ck.gT + i * ck.ge;
-  double *jn = sm, *je = jn + (c + g) * n, *xs = sm + ck.lds_tail, *us = xs + n;
+  const RecoverLds lds = recover_lds(ck, ncols);
+  double *jn = sm, *je = jn + (c + g) * n, *xs = jn + lds.jn, *us = xs + n;
   // column 0's small reads (stagewise solution, right-hand side and weight of the lane's constraint
   // row) are issued ahead of the stage copy: one HBM round trip per wavefront instead of three
   double pre_x = 0.0, pre_y = 0.0, pre_bn = 0.0, pre_wn = 0.0, pre_be = 0.0, pre_we = 0.0;
@@ -855,6 +912,16 @@ recover_chain_kernel(const ChainKkt ck_in, const double *__restrict__ model_all,
 #ifndef SIP_KKT_APPLY_WAVES
 #define SIP_KKT_APPLY_WAVES 1
 #endif
+// LDS: stage image (lds_item) | the stage's slices of x: x_i | u_i | ydyn_i | ydyn_{i+1} | constraint rows (lds_rows)
+struct ApplyLds {
+  int buf, v;
+  constexpr __host__ __device__ int total() const { return buf + v; }
+};
+constexpr __host__ __device__ __forceinline__ ApplyLds apply_lds(const ChainKkt &ck) {
+  ApplyLds l{};
+  l.buf = ck.lds_item, l.v = 3 * ck.n + ck.m + ck.lds_rows;
+  return l;
+}
 template <int FN = 0, int FM = 0>
 __global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(FN > 0 ? SIP_KKT_APPLY_WAVES : 1, 8)))
 apply_chain_kernel(const ChainKkt ck_in, const int th, const double *__restrict__ model_all,
@@ -890,7 +957,8 @@ apply_chain_kernel(const ChainKkt ck_in, const int th, const double *__restrict_
   const double *x_x = io.x_x + p * io.sx, *x_y = io.x_y + p * io.sy, *x_z = io.x_z + p * io.sz;
   double *y_x = io.y_x + p * io.sx, *y_y = io.y_y + p * io.sy, *y_z = io.y_z + p * io.sz;
 
-  double *buf = sm, *v = buf + ck.lds_item;
+  const ApplyLds lds = apply_lds(ck);
+  double *buf = sm, *v = buf + lds.buf;
   // vector slices in LDS: x_i | u_i | ydyn_i | ydyn_{i+1} | yc_node | z_node | yc_edge | z_edge
   double *vx = v, *vu = vx + n, *vd = vu + m, *vdn = vd + n, *vyc = vdn + n, *vzn = vyc + c, *vye = vzn + g,
          *vze = vye + ce;

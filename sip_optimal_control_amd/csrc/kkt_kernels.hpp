@@ -40,12 +40,22 @@ struct Meta {
   // 1 where a y row is a dynamics row (weight = r2 itself), else 0
   const int *y_is_dyn;
   const long *mo[NUM_BLOCKS]; // model arena block offsets
-  // LDS plan of the staged kernels (doubles): Q accumulator | one model item |
-  // the weighted copy of its Jacobian tail | weighted right-hand side rows
+  // what the LDS partitions of the staged kernels (condense_staged_lds, ...) are made of, in doubles: the largest
+  // Q block | model item | Jacobian tail of an item | count of constraint rows, states or controls of an item
   int lds_q, lds_item, lds_tail, lds_rows;
   // offsets inside the LQR arenas (generic_plan.hpp tables)
   const long *oQ, *od, *oq, *oc, *ox, *oy, *oA, *oB, *oM, *oR, *orr, *ou;
 };
+
+// LDS partitions.  Every kernel with dynamic LDS has, next to it, a description of how it divides the buffer: the
+// doubles of every region, in the order the regions lie in the buffer, and `total()`, their sum (for a single region, a
+// function that returns its doubles).  The kernel steps its pointers through the buffer by the description's lengths
+// and the host takes the bytes of the launch from `total()` (lds_bytes), so the two cannot disagree.
+template <class L>
+constexpr size_t lds_bytes(const L &l) {
+  return sizeof(double) * (size_t)l.total();
+}
+constexpr size_t lds_bytes(const int doubles) { return sizeof(double) * (size_t)doubles; }
 
 // The kernels of kkt_kernels.hpp, kkt_theta_kernels.hpp and kkt_theta_chain_kernels.hpp that are no templates belong
 // to sip_kkt_amd.hip alone.  kkt_chain_kernels.hip, which includes these headers for the structs and device functions
@@ -328,6 +338,38 @@ __device__ __forceinline__ double sub_weighted_w(double acc, const double *J, in
   return acc;
 }
 
+// LDS of the staged kernels (Meta::lds_*).  condense: Q accumulator | one model item | the weighted copy of its
+// Jacobian tail | weighted right-hand side rows
+struct CondenseStagedLds {
+  int Qacc, buf, jw, wr;
+  constexpr __host__ __device__ int total() const { return Qacc + buf + jw + wr; }
+};
+constexpr __host__ __device__ __forceinline__ CondenseStagedLds condense_staged_lds(const Meta &mt) {
+  CondenseStagedLds l{};
+  l.Qacc = mt.lds_q, l.buf = mt.lds_item, l.jw = mt.lds_tail, l.wr = mt.lds_rows;
+  return l;
+}
+// rhs: Jacobian tail | weighted right-hand side rows
+struct RhsStagedLds {
+  int buf, wr;
+  constexpr __host__ __device__ int total() const { return buf + wr; }
+};
+constexpr __host__ __device__ __forceinline__ RhsStagedLds rhs_staged_lds(const Meta &mt) {
+  RhsStagedLds l{};
+  l.buf = mt.lds_tail, l.wr = mt.lds_rows;
+  return l;
+}
+// recover: Jacobian tail | x of the node | u of an edge (lds_rows >= max n, max m)
+struct RecoverStagedLds {
+  int buf, xs, us;
+  constexpr __host__ __device__ int total() const { return buf + xs + us; }
+};
+constexpr __host__ __device__ __forceinline__ RecoverStagedLds recover_staged_lds(const Meta &mt) {
+  RecoverStagedLds l{};
+  l.buf = mt.lds_tail, l.xs = mt.lds_rows, l.us = mt.lds_rows;
+  return l;
+}
+
 #ifndef SIP_KKT_CHAIN_UNIT
 template <bool WITH_RHS>
 __global__ void __launch_bounds__(TPB)
@@ -335,7 +377,8 @@ condense_staged_kernel(const Meta mt, const double *__restrict__ model_all, cons
                        const double *__restrict__ inv_all, double *__restrict__ in0_all,
                        const double *__restrict__ b_all, double *__restrict__ in1_all, long batch) {
   extern __shared__ double sm[];
-  double *Qacc = sm, *buf = Qacc + mt.lds_q, *jw = buf + mt.lds_item, *wr = jw + mt.lds_tail;
+  const CondenseStagedLds lds = condense_staged_lds(mt);
+  double *Qacc = sm, *buf = Qacc + lds.Qacc, *jw = buf + lds.buf, *wr = jw + lds.jw;
   const long p = blockIdx.x / mt.N;
   const int i = blockIdx.x - (unsigned)(p * mt.N);
   if (p >= batch)
@@ -492,7 +535,8 @@ rhs_staged_kernel(const Meta mt, const double *__restrict__ model_all, const dou
                   const double *__restrict__ inv_all, double *__restrict__ in1_all,
                   const int32_t *__restrict__ status, long batch) {
   extern __shared__ double sm[];
-  double *buf = sm, *wr = buf + mt.lds_tail;
+  const RhsStagedLds lds = rhs_staged_lds(mt);
+  double *buf = sm, *wr = buf + lds.buf;
   const long p = blockIdx.x / mt.N;
   const int i = blockIdx.x - (unsigned)(p * mt.N);
   if (p >= batch || (status != nullptr && status[p] != 0))
@@ -546,7 +590,8 @@ recover_staged_kernel(const Meta mt, const double *__restrict__ model_all, const
                       const double *__restrict__ inv_all, const double *__restrict__ out_all,
                       double *__restrict__ sol_all, const int32_t *__restrict__ status, long batch) {
   extern __shared__ double sm[];
-  double *buf = sm, *xs = buf + mt.lds_tail, *us = xs + mt.lds_rows; // lds_rows >= max n, max m
+  const RecoverStagedLds lds = recover_staged_lds(mt);
+  double *buf = sm, *xs = buf + lds.buf, *us = xs + lds.xs;
   const long p = blockIdx.x / mt.N;
   const int i = blockIdx.x - (unsigned)(p * mt.N);
   if (p >= batch || status[p] != 0)

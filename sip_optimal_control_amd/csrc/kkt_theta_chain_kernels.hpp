@@ -45,6 +45,15 @@ struct ChainTheta {
   int lds_item;            // doubles (even) of the largest stage item
 };
 
+// ct.node_len, edge_len and lds_item from p and the dimensions of `ck`
+constexpr __host__ __device__ __forceinline__ ChainTheta chain_theta_derive(const ChainKkt &ck, ChainTheta ct) {
+  const int p = ct.p, last_len = (ck.n + ck.cT + ck.gT + p) * p;
+  ct.node_len = (ck.n + ck.cn + ck.gn + p) * p;
+  ct.edge_len = (2 * ck.n + ck.m + ck.ce + ck.ge + p) * p;
+  ct.lds_item = even(ct.node_len + ct.edge_len > last_len ? ct.node_len + ct.edge_len : last_len);
+  return ct;
+}
+
 struct ThetaStage { // the blocks of one stage's item (LDS)
   const double *NX, *NC, *NG, *NTT, *EX, *EU, *ED, *EC, *EG, *ETT;
   int n, m, c, g, ce, ge, p;
@@ -213,6 +222,15 @@ __device__ __forceinline__ long theta_row_at(const ChainKkt &ck, const ThetaStag
 // q_mod | c_mod | r_mod (helpers.cpp:752-812) of ALL p columns of J_theta for stage i, the same sums in the same
 // order as condense_chain_kernel<rhs only> forms them from an assembled J_theta.
 // LDS: [Jacobian tails (lds_tail) | theta item (ct.lds_item) | weights (lds_rows) | weighted rows, p x lds_rows]
+struct ThetaRhsLds {
+  int jn, th, wl, wr;
+  constexpr __host__ __device__ int total() const { return jn + th + wl + wr; }
+};
+constexpr __host__ __device__ __forceinline__ ThetaRhsLds theta_rhs_lds(const ChainKkt &ck, const ChainTheta &ct) {
+  ThetaRhsLds l{};
+  l.jn = ck.lds_tail, l.th = ct.lds_item, l.wl = ck.lds_rows, l.wr = ct.p * ck.lds_rows;
+  return l;
+}
 template <int FN = 0, int FM = 0>
 __global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(FN > 0 ? SIP_KKT_THETA_WAVES : 1, 8)))
 theta_rhs_chain_kernel(const ChainKkt ck_in, const ChainTheta ct, const double *__restrict__ model_all,
@@ -227,7 +245,8 @@ theta_rhs_chain_kernel(const ChainKkt ck_in, const ChainTheta ct, const double *
   const int n = ck.n, m = ck.m, nn = n * n, nm = n * m, tid = s.tid, P = ct.p, R = ck.lds_rows;
   const int c = s.c, g = s.g, ce = s.ce, ge = s.ge, nrows = s.nrows;
   const bool last = s.last;
-  double *jn = sm, *je = jn + (c + g) * n, *th = sm + ck.lds_tail, *wl = th + ct.lds_item, *wr = wl + R;
+  const ThetaRhsLds lds = theta_rhs_lds(ck, ct);
+  double *jn = sm, *je = jn + (c + g) * n, *th = sm + lds.jn, *wl = th + lds.th, *wr = wl + lds.wl;
   const double w = tid < nrows ? theta_weight_row(s, tid) : 0.0;
   if (last) {
     stage_copy_three(jn, s.item + nn, (c + g) * n, je, s.item, 0, th, s.titem, theta_item_len(ck, ct, true), tid);
@@ -281,6 +300,17 @@ theta_rhs_chain_kernel(const ChainKkt ck_in, const ChainTheta ct, const double *
 // p x p share of  sum d2L_dtheta2 - J_theta^T K^-1 J_theta  (:389-398) -> s_part[problem][stage][a + p b].
 // LDS: [Jacobian tails (lds_tail) | theta item | x_i|u_i of the columns, p (n + m) | y_{i+1} of the columns, p n |
 //       multipliers of the columns, p x lds_rows | weights, lds_rows]
+struct ThetaRecoverLds {
+  int jn, th, xs, ys, ms, wl;
+  constexpr __host__ __device__ int total() const { return jn + th + xs + ys + ms + wl; }
+};
+constexpr __host__ __device__ __forceinline__ ThetaRecoverLds theta_recover_lds(const ChainKkt &ck,
+                                                                                const ChainTheta &ct) {
+  ThetaRecoverLds l{};
+  l.jn = ck.lds_tail, l.th = ct.lds_item, l.xs = ct.p * (ck.n + ck.m), l.ys = ct.p * ck.n;
+  l.ms = ct.p * ck.lds_rows, l.wl = ck.lds_rows;
+  return l;
+}
 template <int FN = 0, int FM = 0>
 __global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(FN > 0 ? SIP_KKT_THETA_WAVES : 1, 8)))
 theta_recover_chain_kernel(const ChainKkt ck_in, const ChainTheta ct, const double *__restrict__ model_all,
@@ -297,8 +327,9 @@ theta_recover_chain_kernel(const ChainKkt ck_in, const ChainTheta ct, const doub
   const int c = s.c, g = s.g, ce = s.ce, ge = s.ge, nrows = s.nrows, per = n + m;
   const bool last = s.last;
   const long kkt = (long)ck.x_dim + ck.y_dim + ck.z_dim;
-  double *jn = sm, *je = jn + (c + g) * n, *th = sm + ck.lds_tail, *xs = th + ct.lds_item, *ys = xs + P * per,
-         *ms = ys + P * n, *wl = ms + P * R;
+  const ThetaRecoverLds lds = theta_recover_lds(ck, ct);
+  double *jn = sm, *je = jn + (c + g) * n, *th = sm + lds.jn, *xs = th + lds.th, *ys = xs + lds.xs, *ms = ys + lds.ys,
+         *wl = ms + lds.ms;
   const double w = tid < nrows ? theta_weight_row(s, tid) : 0.0;
   // the stagewise solutions of the columns: requested before the stage copies (one HBM round trip, not two)
   constexpr int UX = 2;
@@ -381,7 +412,7 @@ theta_recover_chain_kernel(const ChainKkt ck_in, const ChainTheta ct, const doub
 
 #ifndef SIP_KKT_CHAIN_UNIT
 // S = sum of the stage partials (in stage order) + diag(r1_theta), then LLT in place (helpers.cpp:399-407).
-// One workgroup per problem.  LDS: p x p.
+// One workgroup per problem.  LDS: S, p x p (theta_schur_lds, kkt_theta_kernels.hpp).
 __global__ void __launch_bounds__(TPB)
 theta_schur_reduce_kernel(const int nstages, const int p, const int sx, const double *__restrict__ r1_all,
                           const double *__restrict__ s_part, double *__restrict__ S_all,
@@ -440,6 +471,15 @@ theta_schur_reduce_kernel(const int nstages, const int p, const int sx, const do
 // The stage's share of J_theta^T v for a stagewise vector v = [x | y | z] (the solve: v = K^-1 b, helpers.cpp:920-928)
 // -> d_part[problem][stage][a].  LDS: [theta item | x_i|u_i rows of v (n + m) | dynamics rows of node i+1 (n) |
 // constraint rows (lds_rows)]
+struct ThetaDotLds {
+  int th, vx, vd, vr;
+  constexpr __host__ __device__ int total() const { return th + vx + vd + vr; }
+};
+constexpr __host__ __device__ __forceinline__ ThetaDotLds theta_dot_lds(const ChainKkt &ck, const ChainTheta &ct) {
+  ThetaDotLds l{};
+  l.th = ct.lds_item, l.vx = ck.n + ck.m, l.vd = ck.n, l.vr = ck.lds_rows;
+  return l;
+}
 template <int FN = 0, int FM = 0>
 __global__ void __launch_bounds__(TPB)
 theta_dot_chain_kernel(const ChainKkt ck_in, const ChainTheta ct, const double *__restrict__ theta_all,
@@ -453,7 +493,8 @@ theta_dot_chain_kernel(const ChainKkt ck_in, const ChainTheta ct, const double *
   const int n = ck.n, m = ck.m, tid = s.tid, P = ct.p, per = n + m;
   const bool last = s.last;
   const long kkt = (long)ck.x_dim + ck.y_dim + ck.z_dim;
-  double *th = sm, *vx = th + ct.lds_item, *vd = vx + per, *vr = vd + n;
+  const ThetaDotLds lds = theta_dot_lds(ck, ct);
+  double *th = sm, *vx = th + lds.th, *vd = vx + lds.vx, *vr = vd + lds.vd;
   const double *v = v_all + s.p * kkt;
   // lanes 0 .. per-1: x_i | u_i; the next n: the dynamics rows of node i + 1; then the constraint rows
   double val = 0.0;
@@ -498,6 +539,21 @@ theta_dot_chain_kernel(const ChainKkt ck_in, const ChainTheta ct, const double *
 // the result does not depend on scheduling).
 // LDS per wavefront: [theta item | x_i|u_i (n + m) | dynamics rows of node i+1 (n) | constraint rows (lds_rows) |
 //                     theta (p, even) | y_theta accumulator (p, even)]
+// The regions of ONE wavefront's part (`each` doubles: their sum); the parts of the wavefronts follow each other.
+// x_i|u_i (vx) and the dynamics rows (vd: vxd - vx doubles) are padded to an even length together and `each` is even:
+// the items of all wavefronts stay 16-byte aligned.  total(): of a workgroup of `waves` wavefronts.
+constexpr int APPLY_THETA_MAX_WAVES = 8;
+struct ApplyThetaLds {
+  int th, vx, vxd, vr, tv, yacc, each, waves;
+  constexpr __host__ __device__ int total() const { return waves * each; }
+};
+constexpr __host__ __device__ __forceinline__ ApplyThetaLds apply_theta_lds(const ChainKkt &ck, const ChainTheta &ct,
+                                                                            const int waves) {
+  ApplyThetaLds l{};
+  l.th = ct.lds_item, l.vx = ck.n + ck.m, l.vxd = even(2 * ck.n + ck.m), l.vr = ck.lds_rows;
+  l.tv = even(ct.p), l.yacc = even(ct.p), l.each = l.th + l.vxd + l.vr + l.tv + l.yacc, l.waves = waves;
+  return l;
+}
 template <int FN = 0, int FM = 0>
 __global__ void __launch_bounds__(512)
 apply_theta_chain_kernel(const ChainKkt ck_in, const ChainTheta ct, const double *__restrict__ theta_all,
@@ -507,11 +563,12 @@ apply_theta_chain_kernel(const ChainKkt ck_in, const ChainTheta ct, const double
   const long prob = blockIdx.x;
   if (prob >= batch)
     return;
-  const int n = ck.n, m = ck.m, T = ck.T, P = ct.p, per = n + m, R = ck.lds_rows, Pe = (P + 1) & ~1;
+  const int n = ck.n, m = ck.m, T = ck.T, P = ct.p, per = n + m;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
-  const int vlen = (per + n + 1) & ~1;                // x_i|u_i and the dynamics rows, padded to an even length
-  const int wl = ct.lds_item + vlen + R + 2 * Pe;     // doubles per wavefront (even: the items stay 16-byte aligned)
-  double *th = sm + wave * wl, *vx = th + ct.lds_item, *vd = vx + per, *vr = vx + vlen, *tv = vr + R, *yacc = tv + Pe;
+  const ApplyThetaLds lds = apply_theta_lds(ck, ct, waves);
+  const int wl = lds.each; // doubles per wavefront
+  double *th = sm + wave * wl, *vx = th + lds.th, *vd = vx + lds.vx, *vr = vx + lds.vxd, *tv = vr + lds.vr,
+         *yacc = tv + lds.tv;
   const int parts = io.parts;
   const bool pH = parts & AP_H, pC = parts & AP_C, pCT = parts & AP_CT, pG = parts & AP_G, pGT = parts & AP_GT,
              pR = parts & AP_REG;
@@ -645,7 +702,7 @@ apply_theta_chain_kernel(const ChainKkt ck_in, const ChainTheta ct, const double
     for (int a = lane; a < P; a += 64) {
       double acc = 0.0;
       for (int w = 0; w < waves; ++w)
-        acc += (sm + w * wl + (wl - Pe))[a];
+        acc += (sm + w * wl + (wl - lds.yacc))[a];
       if (pR)
         acc += r1_all[prob * (sx + P) + sx + a] * tv[a];
       y_x[sx + a] += acc;
@@ -654,14 +711,15 @@ apply_theta_chain_kernel(const ChainKkt ck_in, const ChainTheta ct, const double
 
 #ifndef SIP_KKT_CHAIN_UNIT
 // theta = S^-1 (b_theta - J^T K^-1 b) with J^T K^-1 b from the stage partials; sol = K^-1 b - (K^-1 J) theta,
-// re-inserted as [x | theta | y | z]  (helpers.cpp:920-950).  One workgroup per problem.  LDS: p.
+// re-inserted as [x | theta | y | z]  (helpers.cpp:920-950).  One workgroup per problem.  LDS: theta, p
+// (theta_finish_lds, kkt_theta_kernels.hpp).
 __global__ void __launch_bounds__(TPB)
 theta_finish_parts_kernel(const int nstages, const int p, const int sx, const long skkt,
                           const double *__restrict__ b_all, const double *__restrict__ d_part,
                           const double *__restrict__ KJ_all, const double *__restrict__ S_all,
                           const double *__restrict__ sw_all, double *__restrict__ sol_all,
                           const int32_t *__restrict__ status, const long batch) {
-  extern __shared__ double sm[]; // theta (p)
+  extern __shared__ double sm[]; // theta_finish_lds(p)
   const long prob = blockIdx.x;
   if (prob >= batch || status[prob] != 0)
     return;

@@ -77,12 +77,14 @@ theta_jacobian_kernel(const Meta mt, const ThetaMeta th, const double *__restric
 
 // S = sum d2L_dtheta2 + diag(r1_theta) - J^T (K^-1 J), then LLT in place (helpers.cpp:389-407).
 // One workgroup per problem; lane q owns entry (row a, col b) = (q % p, q / p).
+// LDS (here and in theta_schur_reduce_kernel): S, p x p doubles
+constexpr __host__ __device__ int theta_schur_lds(const int p) { return p * p; }
 __global__ void __launch_bounds__(TPB)
 theta_schur_kernel(const Meta mt, const ThetaMeta th, const double *__restrict__ theta_all,
                    const double *__restrict__ r1_all, const double *__restrict__ J_all,
                    const double *__restrict__ KJ_all, double *__restrict__ S_all, int32_t *__restrict__ status,
                    long batch, int fail_code) {
-  extern __shared__ double sm[]; // p * p
+  extern __shared__ double sm[]; // theta_schur_lds(p)
   const long prob = blockIdx.x;
   if (prob >= batch || status[prob] != 0)
     return;
@@ -233,12 +235,14 @@ theta_strip_kernel(const double *__restrict__ b_all, double *__restrict__ out_al
 
 // theta = S^-1 (b_theta - J^T K^-1 b); sol = K^-1 b - (K^-1 J) theta, re-inserted as
 // [x | theta | y | z]  (helpers.cpp:920-950).  One workgroup per problem.
+// LDS (here and in theta_finish_parts_kernel): theta, p doubles
+constexpr __host__ __device__ int theta_finish_lds(const int p) { return p; }
 __global__ void __launch_bounds__(TPB)
 theta_finish_kernel(const Meta mt, const ThetaMeta th, const double *__restrict__ b_all,
                     const double *__restrict__ J_all, const double *__restrict__ KJ_all,
                     const double *__restrict__ S_all, const double *__restrict__ sw_all,
                     double *__restrict__ sol_all, const int32_t *__restrict__ status, long batch) {
-  extern __shared__ double sm[]; // theta (p)
+  extern __shared__ double sm[]; // theta_finish_lds(p)
   const long prob = blockIdx.x;
   if (prob >= batch || status[prob] != 0)
     return;

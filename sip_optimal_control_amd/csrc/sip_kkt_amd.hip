@@ -61,7 +61,6 @@ struct sip_kkt_plan {
   sip_lqr_plan *chain_sym = nullptr;
   int chain_pipe = 0;         // > 0: stages per wavefront of the software-pipelined condensation
   sipamd::kkt::ChainKkt ck{};
-  size_t lds_chain_condense = 0, lds_chain_recover = 0, lds_chain_apply = 0;
   // theta (sip_kkt_plan_set_theta)
   int theta_dim = 0;
   std::vector<long> toff[sipamd::kkt::TH_NUM_BLOCKS];
@@ -79,7 +78,6 @@ struct sip_kkt_plan {
   bool tree_fused = false;
   size_t at_tree_scratch = 0;
   sipamd::kkt::ChainTheta ct{};
-  size_t lds_theta_rhs = 0, lds_theta_recover = 0, lds_theta_dot = 0;
   // first-order arena (sip_kkt_gather_first_order): block offsets, their copy at fo_at of d_longs -- uploaded by
   // sip_kkt_plan_create and again by sip_kkt_plan_set_theta (df_dtheta then has theta_dim entries), never at first use
   std::vector<long> foff[sipamd::kkt::FO_NUM_BLOCKS];
@@ -88,7 +86,6 @@ struct sip_kkt_plan {
   bool fo_uniform = false; // chain_kernels plans: gather_first_order_uniform (arithmetic offsets)
   sipamd::kkt::FoUniform fu{};
   bool staged = false; // LDS-staged kernels (false: items too large for LDS, or SIP_KKT_VARIANT=direct)
-  size_t lds_condense = 0, lds_rhs = 0, lds_recover = 0;
   std::string name;
 
   ~sip_kkt_plan() {
@@ -110,6 +107,7 @@ struct sip_kkt_plan {
 namespace {
 
 using sipamd::kkt::Meta;
+namespace kkt = sipamd::kkt; // (the LDS descriptions next to the kernels, and what is derived from them: kkt::...)
 
 std::vector<int> dims_or_zero(const int *src, int count) {
   return src ? std::vector<int>(src, src + count) : std::vector<int>((size_t)count, 0);
@@ -254,7 +252,6 @@ bool uniform_constraints(const sip_kkt_plan &p) {
       return false;
   return p.sd[0] <= 32 && p.cd[0] <= 32;
 }
-int even(int v) { return (v + 1) / 2 * 2; }
 
 // b != nullptr (fused factor+solve on the staged kernels): also builds q_mod, r_mod, c_mod.
 // split (chain kernels only): mats for sip_lqr_factor_solve_split -- no A | B in it.
@@ -262,12 +259,10 @@ hipError_t launch_condense(const sip_kkt_plan *p, const Regions &r, const double
                            const double *r1, const double *r2, const double *r3, const double *b,
                            hipStream_t s, const bool split = false, const bool sym = false) {
   sipamd::kkt::ChainKkt ck = p->ck;
-  if (split) {
-    const int n = ck.n, m = ck.m;
-    const int qlen = sym ? n * (n + 1) / 2 : n * n, rlen = sym ? m * (m + 1) / 2 : m * m;
+  if (split) { // the same chain, its mats in the split (and packed) layout
     ck.split = 1, ck.sym = sym ? 1 : 0;
-    ck.mats_stage = (qlen + n) + (n * m + rlen);
-    ck.mats_len = (long)(ck.T + 1) * (qlen + n) + (long)ck.T * (n * m + rlen);
+    ck = kkt::chain_kkt_derive(ck);
+    ck.mats_len = kkt::chain_mats_len(ck);
   }
   hipError_t e = sipamd::zero_async(r.reg, (size_t)p->batch * sizeof(int), s); // a kernel: stream_fill.hpp
   if (e != hipSuccess)
@@ -282,11 +277,7 @@ hipError_t launch_condense(const sip_kkt_plan *p, const Regions &r, const double
   const bool odd_tail = pipe && ((ck.n * ck.n + (ck.cT + ck.gT) * ck.n) & 1);
   const long pipe_batch = odd_tail ? (long)p->batch - 1 : (long)p->batch;
   const unsigned pipe_grid = pipe ? (unsigned)((pipe_batch * p->N + p->chain_pipe - 1) / p->chain_pipe) : 0u;
-  // LDS of the chain kernels: image | weights | weighted rows | r1 slice | the outgoing block of mats -- of THIS
-  // layout (split / packed blocks are smaller: more workgroups per CU)
-  const size_t lds_chain = p->chain_kernels ? sizeof(double) * ((size_t)ck.lds_item + 2 * (size_t)ck.lds_rows +
-                                                                 (size_t)even(ck.n + ck.m) + (size_t)ck.mats_stage)
-                                            : 0;
+  const size_t lds_chain = p->chain_kernels ? kkt::lds_bytes(kkt::condense_lds(ck, true, 1)) : 0; // of THIS layout
   // one-stage kernel over `nb` problems starting at problem `q0`
   auto one_stage = [&](const long q0, const long nb) {
     const long kkt_len = (long)p->x_dim + p->y_dim + p->z_dim;
@@ -316,11 +307,12 @@ hipError_t launch_condense(const sip_kkt_plan *p, const Regions &r, const double
   }
   else if (p->staged && b != nullptr) // condensation and right-hand side from one staging of the model
     hipLaunchKernelGGL(sipamd::kkt::condense_staged_kernel<true>, dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
-                       p->lds_condense, s, p->meta, model, r1, r.inv, r.in0, b, r.in1, (long)p->batch);
+                       kkt::lds_bytes(kkt::condense_staged_lds(p->meta)), s, p->meta, model, r1, r.inv, r.in0, b,
+                       r.in1, (long)p->batch);
   else if (p->staged)
     hipLaunchKernelGGL(sipamd::kkt::condense_staged_kernel<false>, dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
-                       p->lds_condense, s, p->meta, model, r1, r.inv, r.in0, (const double *)nullptr,
-                       (double *)nullptr, (long)p->batch);
+                       kkt::lds_bytes(kkt::condense_staged_lds(p->meta)), s, p->meta, model, r1, r.inv, r.in0,
+                       (const double *)nullptr, (double *)nullptr, (long)p->batch);
   else
     hipLaunchKernelGGL(sipamd::kkt::condense_kernel, dim3(item_grid(p)), dim3(sipamd::kkt::TPB), 0, s, p->meta,
                        model, r1, r.inv, r.in0, (long)p->batch);
@@ -333,43 +325,34 @@ hipError_t launch_merge(const sip_kkt_plan *p, const Regions &r, int32_t *status
   return hipGetLastError();
 }
 
-// The generic right-hand-side kernels with the LQR offsets of `mt` (tree plans: p->meta, or a copy that places
-// q | c, r in the column layout of sip_lqr_tree_solve_multi).
-hipError_t launch_rhs_meta(const sip_kkt_plan *p, const Meta &mt, const Regions &r, const double *model,
-                           const double *b, const int32_t *status, hipStream_t s) {
-  if (p->staged)
-    hipLaunchKernelGGL(sipamd::kkt::rhs_staged_kernel, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_rhs, s,
-                       mt, model, b, r.inv, r.in1, status, (long)p->batch);
+// Right-hand sides of one column.  The generic kernels take the LQR offsets of `mt`: p->meta, or (tree plans) a copy
+// that places q | c, r in the column layout of sip_lqr_tree_solve_multi.
+hipError_t launch_rhs(const sip_kkt_plan *p, const Meta &mt, const Regions &r, const double *model, const double *b,
+                      const int32_t *status, hipStream_t s) {
+  if (p->chain_kernels)
+    hipLaunchKernelGGL(p->k->rhs, dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
+                       kkt::lds_bytes(kkt::condense_lds(p->ck, false, 1)), s, p->ck, model, (const double *)nullptr,
+                       r.inv, r.in0, b, r.in1, (long)p->batch, status, 1, 0L, 0L);
+  else if (p->staged)
+    hipLaunchKernelGGL(sipamd::kkt::rhs_staged_kernel, dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
+                       kkt::lds_bytes(kkt::rhs_staged_lds(mt)), s, mt, model, b, r.inv, r.in1, status,
+                       (long)p->batch);
   else
     hipLaunchKernelGGL(sipamd::kkt::rhs_kernel, dim3(item_grid(p)), dim3(sipamd::kkt::TPB), 0, s, mt, model, b,
                        r.inv, r.in1, status, (long)p->batch);
   return hipGetLastError();
 }
 
-hipError_t launch_rhs(const sip_kkt_plan *p, const Regions &r, const double *model, const double *b,
-                      const int32_t *status, hipStream_t s) {
-  if (p->chain_kernels)
-    hipLaunchKernelGGL(p->k->rhs, dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
-                       // (rhs only: the constraint Jacobians | weights | weighted rows)
-                       sizeof(double) * ((size_t)p->ck.lds_tail + 2 * (size_t)p->ck.lds_rows), s, p->ck, model,
-                       (const double *)nullptr, r.inv, r.in0, b, r.in1, (long)p->batch, status, 1, 0L, 0L);
-  else if (p->staged)
-    hipLaunchKernelGGL(sipamd::kkt::rhs_staged_kernel, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_rhs, s,
-                       p->meta, model, b, r.inv, r.in1, status, (long)p->batch);
-  else
-    hipLaunchKernelGGL(sipamd::kkt::rhs_kernel, dim3(item_grid(p)), dim3(sipamd::kkt::TPB), 0, s, p->meta, model,
-                       b, r.inv, r.in1, status, (long)p->batch);
-  return hipGetLastError();
-}
-
 hipError_t launch_recover(const sip_kkt_plan *p, const Regions &r, const double *model, const double *b,
                           double *sol, const int32_t *status, hipStream_t s) {
   if (p->chain_kernels)
-    hipLaunchKernelGGL(p->k->recover, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_chain_recover, s, p->ck, model,
-                       b, r.inv, r.out, sol, status, (long)p->batch, 1, 0L, 0L, 0L);
+    hipLaunchKernelGGL(p->k->recover, dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
+                       kkt::lds_bytes(kkt::recover_lds(p->ck, 1)), s, p->ck, model, b, r.inv, r.out, sol, status,
+                       (long)p->batch, 1, 0L, 0L, 0L);
   else if (p->staged)
     hipLaunchKernelGGL(sipamd::kkt::recover_staged_kernel, dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
-                       p->lds_recover, s, p->meta, model, b, r.inv, r.out, sol, status, (long)p->batch);
+                       kkt::lds_bytes(kkt::recover_staged_lds(p->meta)), s, p->meta, model, b, r.inv, r.out, sol,
+                       status, (long)p->batch);
   else
     hipLaunchKernelGGL(sipamd::kkt::recover_kernel, dim3(item_grid(p)), dim3(sipamd::kkt::TPB), 0, s, p->meta,
                        model, b, r.inv, r.out, sol, status, (long)p->batch);
@@ -397,8 +380,9 @@ int apply_blocks(const sip_kkt_plan *p, const double *d_model, const double *d_t
     return report(on_device.err, what);
   const int th = d_theta != nullptr ? p->theta_dim : 0;
   if (p->chain_kernels) {
-    hipLaunchKernelGGL(p->k->apply, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_chain_apply, s, p->ck, th,
-                       d_model, d_w, d_r1, d_r2, d_r3, io, (long)p->batch);
+    hipLaunchKernelGGL(p->k->apply, dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
+                       kkt::lds_bytes(kkt::apply_lds(p->ck)), s, p->ck, th, d_model, d_w, d_r1, d_r2, d_r3, io,
+                       (long)p->batch);
   } else {
     sipamd::kkt::Meta wide = p->meta; // x-space = [stagewise x | theta]
     wide.theta_dim = th;
@@ -407,13 +391,11 @@ int apply_blocks(const sip_kkt_plan *p, const double *d_model, const double *d_t
   }
   if (th > 0 && p->chain_theta) {
     // W wavefronts per problem, as many as 64 KiB of LDS hold (kkt_theta_chain_kernels.hpp)
-    const size_t pe = ((size_t)th + 1) & ~(size_t)1;
-    const size_t vlen = ((size_t)(2 * p->ck.n + p->ck.m) + 1) & ~(size_t)1;
-    const size_t per_wave = sizeof(double) * ((size_t)p->ct.lds_item + vlen + p->ck.lds_rows + 2 * pe);
-    int waves = (int)std::min<size_t>(8, (64 * 1024) / per_wave);
-    waves = std::max(1, std::min(waves, p->N));
-    hipLaunchKernelGGL(p->k->apply_theta, dim3((unsigned)p->batch), dim3(64 * waves), per_wave * waves, s, p->ck, p->ct,
-                       d_theta, d_r1, io, (long)p->batch);
+    const int fit = kkt::lds_count_that_fits(kkt::apply_theta_lds(p->ck, p->ct, 1), kkt::APPLY_THETA_MAX_WAVES);
+    const int waves = std::max(1, std::min(fit, p->N));
+    hipLaunchKernelGGL(p->k->apply_theta, dim3((unsigned)p->batch), dim3(64 * waves),
+                       kkt::lds_bytes(kkt::apply_theta_lds(p->ck, p->ct, waves)), s, p->ck, p->ct, d_theta, d_r1, io,
+                       (long)p->batch);
   } else if (th > 0)
     hipLaunchKernelGGL(sipamd::kkt::apply_theta_kernel, dim3((unsigned)p->batch), dim3(sipamd::kkt::TPB), 0, s,
                        p->meta, p->theta_meta, d_theta, d_r1, io, (long)p->batch);
@@ -597,23 +579,22 @@ int sip_kkt_plan_create(int64_t batch, int num_edges, int root, const int *edge_
       child_edges[cursor[p->parents[e]]++] = e; // stable in the edge index (lqr.cpp:588-598)
   }
 
-  // LDS plan of the staged kernels
-  int lds_q = 0, lds_item = 0, lds_tail = 0, lds_rows = 1;
+  // what the LDS partitions of the staged kernels are made of (kkt_kernels.hpp: kkt::condense_staged_lds, ...)
+  Meta &mt = p->meta;
+  mt.lds_q = mt.lds_item = mt.lds_tail = 0, mt.lds_rows = 1;
   for (int i = 0; i < N; ++i) {
     const int n = p->sd[i], cg = p->ncd[i] + p->ngd[i];
-    lds_q = std::max(lds_q, n * n), lds_item = std::max(lds_item, n * n + cg * n);
-    lds_tail = std::max(lds_tail, cg * n), lds_rows = std::max(lds_rows, std::max(cg, n));
+    mt.lds_q = std::max(mt.lds_q, n * n), mt.lds_item = std::max(mt.lds_item, n * n + cg * n);
+    mt.lds_tail = std::max(mt.lds_tail, cg * n), mt.lds_rows = std::max(mt.lds_rows, std::max(cg, n));
   }
   for (int e = 0; e < E; ++e) {
     const int n = p->sd[p->parents[e]], nc = p->sd[p->children[e]], m = p->cd[e], cg = p->ecd[e] + p->egd[e];
-    lds_item = std::max(lds_item, n * n + n * m + m * m + nc * n + nc * m + cg * (n + m));
-    lds_tail = std::max(lds_tail, cg * (n + m)), lds_rows = std::max(lds_rows, std::max(cg, m));
+    mt.lds_item = std::max(mt.lds_item, n * n + n * m + m * m + nc * n + nc * m + cg * (n + m));
+    mt.lds_tail = std::max(mt.lds_tail, cg * (n + m)), mt.lds_rows = std::max(mt.lds_rows, std::max(cg, m));
   }
-  p->lds_condense = sizeof(double) * ((size_t)lds_q + lds_item + lds_tail + lds_rows);
-  p->lds_rhs = sizeof(double) * ((size_t)lds_tail + lds_rows);
-  p->lds_recover = sizeof(double) * ((size_t)lds_tail + 2 * (size_t)lds_rows);
   const char *variant = std::getenv("SIP_KKT_VARIANT");
-  p->staged = p->lds_condense <= 48 * 1024 && !(variant && std::strcmp(variant, "direct") == 0);
+  p->staged = kkt::lds_bytes(kkt::condense_staged_lds(p->meta)) <= 48 * 1024 &&
+              !(variant && std::strcmp(variant, "direct") == 0);
   if (p->chain != nullptr && p->staged && uniform_constraints(*p)) {
     sipamd::kkt::ChainKkt &ck = p->ck;
     ck.n = p->sd[0], ck.m = p->cd[0], ck.T = E;
@@ -621,23 +602,12 @@ int sip_kkt_plan_create(int64_t batch, int num_edges, int root, const int *edge_
     if (E == 1) // one interior node only: its dimensions are the "interior" ones
       ck.cn = p->ncd[0], ck.gn = p->ngd[0];
     ck.cT = p->ncd[E], ck.gT = p->ngd[E], ck.ce = p->ecd[0], ck.ge = p->egd[0];
-    const int n = ck.n, mm = ck.m;
-    ck.node_len = n * n + (ck.cn + ck.gn) * n;
-    ck.edge_len = 2 * n * n + 2 * n * mm + mm * mm + (ck.ce + ck.ge) * (n + mm);
-    ck.model_len = p->model_len, ck.x_dim = p->x_dim, ck.y_dim = p->y_dim, ck.z_dim = p->z_dim;
-    ck.mats_stage = (n * n + n) + (n * n + 2 * n * mm + mm * mm), ck.vecs_stage = 2 * n + mm;
-    ck.mats_len = p->in0_len, ck.vecs_len = p->in1_len;
     ck.split = 0, ck.sym = 0;
-    const int cgn = std::max(ck.cn + ck.gn, ck.cT + ck.gT), cge = ck.ce + ck.ge;
-    ck.lds_item = even(n * n + cgn * n + ck.edge_len);
-    ck.lds_tail = even(cgn * n + cge * (n + mm)); // recover: every Jacobian of a stage
-    ck.lds_rows = even(cgn + cge);                // condense: weights | weighted rhs rows
-    // model image | weights | weighted rhs rows | r1 of the stage | the stage block of mats on its way out
-    p->lds_chain_condense = sizeof(double) * ((size_t)ck.lds_item + 2 * (size_t)ck.lds_rows + even(n + mm) + ck.mats_stage);
-    p->lds_chain_recover = sizeof(double) * ((size_t)ck.lds_tail + n + mm);
-    p->lds_chain_apply = sizeof(double) * ((size_t)ck.lds_item + 3 * n + mm + (size_t)ck.lds_rows);
+    ck = kkt::chain_kkt_derive(ck);
+    ck.model_len = p->model_len, ck.x_dim = p->x_dim, ck.y_dim = p->y_dim, ck.z_dim = p->z_dim;
+    ck.mats_len = p->in0_len, ck.vecs_len = p->in1_len;
     // lane maps of the chain kernels: state rows on lanes 0..n-1, control rows on lanes 32..32+m-1
-    p->chain_kernels = p->lds_chain_condense <= 48 * 1024 && n <= 32 && mm <= 32 &&
+    p->chain_kernels = kkt::lds_bytes(kkt::condense_lds(ck, true, 1)) <= 48 * 1024 && ck.n <= 32 && ck.m <= 32 &&
                        !(variant && std::strcmp(variant, "tables") == 0);
   }
   if (p->chain_kernels) {
@@ -727,10 +697,9 @@ int sip_kkt_plan_create(int64_t batch, int num_edges, int root, const int *edge_
   }
   const int *di = (const int *)p->d_ints;
   const long *dl = (const long *)p->d_longs;
-  Meta &m = p->meta;
+  Meta &m = p->meta; // (its lds_* fields are set above, where `staged` is decided)
   m.E = E, m.N = N, m.root = root, m.x_dim = p->x_dim, m.y_dim = p->y_dim, m.z_dim = p->z_dim;
   m.model_len = p->model_len, m.in0_len = p->in0_len, m.in1_len = p->in1_len, m.out_len = p->out_len;
-  m.lds_q = lds_q, m.lds_item = lds_item, m.lds_tail = lds_tail, m.lds_rows = lds_rows;
   m.sd = di + a_sd, m.cd = di + a_cd, m.ncd = di + a_ncd, m.ngd = di + a_ngd, m.ecd = di + a_ecd, m.egd = di + a_egd;
   m.parent = di + a_pa, m.child = di + a_ch, m.in_edge = di + a_in;
   m.child_offsets = di + a_co, m.child_edges = di + a_ce, m.y_is_dyn = di + a_dyn;
@@ -841,7 +810,7 @@ int sip_kkt_solve(const sip_kkt_plan *p, const double *d_model, const double *d_
     return report(on_device.err, "sip_kkt_solve(hipSetDevice)");
   hipStream_t s = (hipStream_t)stream;
   const Regions r = regions(p, d_work);
-  hipError_t e = launch_rhs(p, r, d_model, d_b, d_status, s);
+  hipError_t e = launch_rhs(p, p->meta, r, d_model, d_b, d_status, s);
   if (e != hipSuccess)
     return report(e, "sip_kkt_solve(rhs)");
   const int rc = p->chain        ? sip_lqr_solve(p->chain, r.in0, r.in1, r.out, r.gain, r.lqr, s)
@@ -880,7 +849,7 @@ int sip_kkt_factor_solve(const sip_kkt_plan *p, const double *d_model, const dou
   const bool sym = split && p->chain_sym != nullptr;
   hipError_t e = launch_condense(p, r, d_model, d_w, d_r1, d_r2, d_r3, fused_rhs ? d_b : nullptr, s, split, sym);
   if (e == hipSuccess && !fused_rhs)
-    e = launch_rhs(p, r, d_model, d_b, nullptr, s);
+    e = launch_rhs(p, p->meta, r, d_model, d_b, nullptr, s);
   if (e != hipSuccess)
     return report(e, "sip_kkt_factor_solve(condense)");
   const int rc = split ? sip_lqr_factor_solve_split(sym ? p->chain_sym : p->chain, r.in0, d_model + ab_off,
@@ -999,21 +968,41 @@ size_t theta_j_scalars(const sip_kkt_plan *p) { // per problem
   const size_t skkt = (size_t)p->x_dim + p->y_dim + p->z_dim, th = (size_t)p->theta_dim;
   return p->chain_theta ? (size_t)p->N * (th * th + th) : skkt * th;
 }
+// The regions of the theta workspace: their byte offsets by one walk, which also gives the workspace's size (`end`).
+struct ThetaOffsets {
+  size_t J, KJ, S, rhs_sw, sol_sw, vecs_cols, lsol_cols, cws, end;
+};
+ThetaOffsets theta_offsets(const sip_kkt_plan *p) {
+  const size_t skkt = (size_t)p->x_dim + p->y_dim + p->z_dim, B = (size_t)p->batch, th = (size_t)p->theta_dim;
+  size_t cur = 0;
+  auto take = [&cur](const size_t bytes) {
+    const size_t at = cur;
+    cur = align256(cur + bytes);
+    return at;
+  };
+  ThetaOffsets o;
+  // (the fused chain passes keep stage partials here instead of J_theta: S_part (N p^2) then d_part (N p) per problem)
+  o.J = take(sizeof(double) * B * theta_j_scalars(p));
+  o.KJ = take(sizeof(double) * B * skkt * th);
+  o.S = take(sizeof(double) * B * th * th);
+  o.rhs_sw = take(sizeof(double) * B * skkt);
+  o.sol_sw = take(sizeof(double) * B * skkt);
+  const size_t cols = sizeof(double) * B * theta_col_scalars(p) * th;
+  o.vecs_cols = take(cols);
+  o.lsol_cols = take(cols);
+  o.cws = take(p->chain_kernels      ? sip_lqr_solve_multi_workspace_bytes(p->chain, p->theta_dim)
+               : p->tree_theta_multi ? sip_lqr_tree_solve_multi_scratch_bytes(p->tree, p->theta_dim)
+                                     : 0);
+  o.end = cur;
+  return o;
+}
 ThetaRegions theta_regions(const sip_kkt_plan *p, void *theta_work) {
-  const size_t skkt = (size_t)p->x_dim + p->y_dim + p->z_dim, B = (size_t)p->batch;
+  const ThetaOffsets o = theta_offsets(p);
   char *w = (char *)theta_work;
   ThetaRegions r;
-  size_t cur = 0;
-  // (the fused chain passes keep stage partials here instead of J_theta: S_part (N p^2) then d_part (N p) per problem)
-  r.J = (double *)(w + cur), cur = align256(cur + sizeof(double) * B * theta_j_scalars(p));
-  r.KJ = (double *)(w + cur), cur = align256(cur + sizeof(double) * B * skkt * p->theta_dim);
-  r.S = (double *)(w + cur), cur = align256(cur + sizeof(double) * B * p->theta_dim * p->theta_dim);
-  r.rhs_sw = (double *)(w + cur), cur = align256(cur + sizeof(double) * B * skkt);
-  r.sol_sw = (double *)(w + cur), cur = align256(cur + sizeof(double) * B * skkt);
-  const size_t cols = sizeof(double) * B * theta_col_scalars(p) * p->theta_dim;
-  r.vecs_cols = (double *)(w + cur), cur = align256(cur + cols);
-  r.lsol_cols = (double *)(w + cur), cur = align256(cur + cols);
-  r.cws = w + cur;
+  r.J = (double *)(w + o.J), r.KJ = (double *)(w + o.KJ), r.S = (double *)(w + o.S);
+  r.rhs_sw = (double *)(w + o.rhs_sw), r.sol_sw = (double *)(w + o.sol_sw);
+  r.vecs_cols = (double *)(w + o.vecs_cols), r.lsol_cols = (double *)(w + o.lsol_cols), r.cws = w + o.cws;
   return r;
 }
 
@@ -1072,9 +1061,7 @@ int sip_kkt_plan_set_theta(sip_kkt_plan *p, int theta_dim) {
     const sipamd::kkt::ChainKkt &ck = p->ck;
     sipamd::kkt::ChainTheta &ct = p->ct;
     ct.p = th, ct.theta_len = at;
-    ct.node_len = (ck.n + ck.cn + ck.gn + th) * th;
-    ct.edge_len = (2 * ck.n + ck.m + ck.ce + ck.ge + th) * th;
-    ct.lds_item = even(std::max(ct.node_len + ct.edge_len, (ck.n + ck.cT + ck.gT + th) * th));
+    ct = kkt::chain_theta_derive(ck, ct);
     bool as_assumed = true; // the blocks of stage i are one item at i (node_len + edge_len), in ThetaBlock order
     for (int i = 0; i < N && as_assumed; ++i) {
       const long base = (long)i * (ct.node_len + ct.edge_len);
@@ -1090,13 +1077,9 @@ int sip_kkt_plan_set_theta(sip_kkt_plan *p, int theta_dim) {
                      p->toff[TH_E_TT][i] == base + ct.node_len + (long)(2 * ck.n + ck.m + ck.ce + ck.ge) * th &&
                      p->parents[i] == i && p->children[i] == i + 1;
     }
-    const size_t per = (size_t)ck.n + ck.m, R = (size_t)ck.lds_rows, P = (size_t)th;
-    p->lds_theta_rhs = sizeof(double) * ((size_t)ck.lds_tail + ct.lds_item + R + P * R);
-    p->lds_theta_recover = sizeof(double) * ((size_t)ck.lds_tail + ct.lds_item + P * per + P * ck.n + P * R + R);
-    p->lds_theta_dot = sizeof(double) * ((size_t)ct.lds_item + per + ck.n + R);
     const char *fe = std::getenv("SIP_KKT_THETA_FUSED");
-    p->chain_theta = as_assumed && std::max(p->lds_theta_rhs, p->lds_theta_recover) <= 64 * 1024 &&
-                     !(fe != nullptr && fe[0] == '0');
+    p->chain_theta = as_assumed && kkt::theta_rhs_lds(ck, ct).total() <= kkt::LDS_DOUBLES &&
+                     kkt::theta_recover_lds(ck, ct).total() <= kkt::LDS_DOUBLES && !(fe != nullptr && fe[0] == '0');
     if (p->chain_theta)
       p->name += " + fused theta passes";
   }
@@ -1123,13 +1106,7 @@ size_t sip_kkt_theta_offset(const sip_kkt_plan *p, int block, int index) {
 size_t sip_kkt_theta_work_bytes(const sip_kkt_plan *p) {
   if (p == nullptr || p->theta_dim < 1)
     return 0;
-  const size_t skkt = (size_t)p->x_dim + p->y_dim + p->z_dim, B = (size_t)p->batch, th = (size_t)p->theta_dim;
-  const size_t cols = align256(sizeof(double) * B * theta_col_scalars(p) * th);
-  const size_t cws = p->chain_kernels      ? align256(sip_lqr_solve_multi_workspace_bytes(p->chain, p->theta_dim))
-                     : p->tree_theta_multi ? align256(sip_lqr_tree_solve_multi_scratch_bytes(p->tree, p->theta_dim))
-                                           : 0;
-  return align256(sizeof(double) * B * theta_j_scalars(p)) + align256(sizeof(double) * B * skkt * th) +
-         align256(sizeof(double) * B * th * th) + 2 * align256(sizeof(double) * B * skkt) + 2 * cols + cws;
+  return theta_offsets(p).end;
 }
 
 int sip_kkt_factor_theta(const sip_kkt_plan *p, const double *d_model, const double *d_theta, const double *d_w,
@@ -1164,22 +1141,23 @@ int sip_kkt_factor_theta(const sip_kkt_plan *p, const double *d_model, const dou
     const Regions r = regions(p, d_work);
     const long colJ = (long)p->batch * skkt, colV = (long)p->batch * p->in1_len;
     double *s_part = t.J;
-    hipLaunchKernelGGL(p->k->theta_rhs, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_theta_rhs, s, p->ck, p->ct,
-                       d_model, d_theta, (const double *)r.inv, t.vecs_cols, colV, (const int32_t *)d_status,
-                       (long)p->batch);
+    hipLaunchKernelGGL(p->k->theta_rhs, dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
+                       kkt::lds_bytes(kkt::theta_rhs_lds(p->ck, p->ct)), s, p->ck, p->ct, d_model, d_theta,
+                       (const double *)r.inv, t.vecs_cols, colV, (const int32_t *)d_status, (long)p->batch);
     if ((e = hipGetLastError()) != hipSuccess)
       return report(e, "sip_kkt_factor_theta(rhs)");
     rc = sip_lqr_solve_multi(p->chain, r.in0, t.vecs_cols, t.lsol_cols, th, r.gain, r.lqr, t.cws, s);
     if (rc != SIP_LQR_OK)
       return rc;
-    hipLaunchKernelGGL(p->k->theta_recover, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_theta_recover, s, p->ck,
-                       p->ct, d_model, d_theta, (const double *)r.inv, (const double *)t.lsol_cols, colV, t.KJ, colJ,
-                       s_part, (const int32_t *)d_status, (long)p->batch);
+    hipLaunchKernelGGL(p->k->theta_recover, dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
+                       kkt::lds_bytes(kkt::theta_recover_lds(p->ck, p->ct)), s, p->ck, p->ct, d_model, d_theta,
+                       (const double *)r.inv, (const double *)t.lsol_cols, colV, t.KJ, colJ, s_part,
+                       (const int32_t *)d_status, (long)p->batch);
     if ((e = hipGetLastError()) != hipSuccess)
       return report(e, "sip_kkt_factor_theta(recover)");
     hipLaunchKernelGGL(sipamd::kkt::theta_schur_reduce_kernel, dim3((unsigned)p->batch), dim3(sipamd::kkt::TPB),
-                       sizeof(double) * (size_t)th * th, s, p->N, th, sx, d_r1, (const double *)s_part, t.S, d_status,
-                       (long)p->batch, (int)SIP_KKT_THETA_SCHUR_FAILURE);
+                       kkt::lds_bytes(kkt::theta_schur_lds(th)), s, p->N, th, sx, d_r1, (const double *)s_part, t.S,
+                       d_status, (long)p->batch, (int)SIP_KKT_THETA_SCHUR_FAILURE);
     return report(hipGetLastError(), "sip_kkt_factor_theta(schur)");
   }
   hipLaunchKernelGGL(sipamd::kkt::theta_jacobian_kernel, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), 0, s, p->meta,
@@ -1191,14 +1169,13 @@ int sip_kkt_factor_theta(const sip_kkt_plan *p, const double *d_model, const dou
     // Jacobians, one Riccati solve per column, the multipliers of all columns from one staging
     const Regions r = regions(p, d_work);
     const long colJ = (long)p->batch * skkt, colV = (long)p->batch * p->in1_len;
-    // (LDS: one block of weighted rows per column; as many columns per launch as 64 KiB hold)
-    const size_t rhs_col_lds = sizeof(double) * (size_t)p->ck.lds_rows;
-    const size_t rhs_lds = sizeof(double) * ((size_t)p->ck.lds_tail + 2 * (size_t)p->ck.lds_rows); // one column
-    const int rhs_cols = 1 + (int)std::min<size_t>((size_t)(th - 1), (64 * 1024 - rhs_lds) / std::max<size_t>(rhs_col_lds, 1));
+    // (as many columns per launch as LDS holds)
+    const int rhs_cols = kkt::lds_count_that_fits(kkt::condense_lds(p->ck, false, 1), th);
     for (int c0 = 0; c0 < th; c0 += rhs_cols) {
       const int nc = std::min(rhs_cols, th - c0);
-      hipLaunchKernelGGL(p->k->rhs, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), rhs_lds + rhs_col_lds * (size_t)(nc - 1),
-                         s, p->ck, d_model, (const double *)nullptr, r.inv, r.in0,
+      hipLaunchKernelGGL(p->k->rhs, dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
+                         kkt::lds_bytes(kkt::condense_lds(p->ck, false, nc)), s, p->ck,
+                         d_model, (const double *)nullptr, r.inv, r.in0,
                          (const double *)t.J + (size_t)c0 * colJ, t.vecs_cols + (size_t)c0 * colV, (long)p->batch,
                          (const int32_t *)d_status, nc, colJ, colV);
     }
@@ -1209,14 +1186,12 @@ int sip_kkt_factor_theta(const sip_kkt_plan *p, const double *d_model, const dou
     rc = sip_lqr_solve_multi(p->chain, r.in0, t.vecs_cols, t.lsol_cols, th, r.gain, r.lqr, t.cws, s);
     if (rc != SIP_LQR_OK)
       return rc;
-    // (LDS: x_i | u_i of every column of a launch)
-    const size_t rec_col_lds = sizeof(double) * (size_t)(p->ck.n + p->ck.m);
-    const int rec_cols = 1 + (int)std::min<size_t>((size_t)(th - 1), (64 * 1024 - p->lds_chain_recover) / rec_col_lds);
+    const int rec_cols = kkt::lds_count_that_fits(kkt::recover_lds(p->ck, 1), th);
     for (int c0 = 0; c0 < th; c0 += rec_cols) {
       const int nc = std::min(rec_cols, th - c0);
-      // (nc == 1: lds_chain_recover alone, on the single-column instantiation)
+      // (nc == 1: the single-column instantiation)
       hipLaunchKernelGGL(nc > 1 ? p->k->recover_cols : p->k->recover, dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
-                         p->lds_chain_recover + rec_col_lds * (size_t)(nc - 1), s, p->ck, d_model,
+                         kkt::lds_bytes(kkt::recover_lds(p->ck, nc)), s, p->ck, d_model,
                          (const double *)t.J + (size_t)c0 * colJ, r.inv, (const double *)t.lsol_cols + (size_t)c0 * colV,
                          t.KJ + (size_t)c0 * colJ, (const int32_t *)d_status, (long)p->batch, nc, colJ, colV, colJ);
     }
@@ -1234,7 +1209,7 @@ int sip_kkt_factor_theta(const sip_kkt_plan *p, const double *d_model, const dou
     Regions rc_ = r;
     for (int col = 0; col < th && e == hipSuccess; ++col) {
       rc_.in1 = t.vecs_cols + (size_t)col * colV;
-      e = launch_rhs_meta(p, cm, rc_, d_model, t.J + (size_t)col * colJ, d_status, s);
+      e = launch_rhs(p, cm, rc_, d_model, t.J + (size_t)col * colJ, d_status, s);
     }
     if (e != hipSuccess)
       return report(e, "sip_kkt_factor_theta(rhs)");
@@ -1262,7 +1237,8 @@ int sip_kkt_factor_theta(const sip_kkt_plan *p, const double *d_model, const dou
                        (int)SIP_KKT_THETA_SCHUR_FAILURE);
   else
     hipLaunchKernelGGL(sipamd::kkt::theta_schur_kernel, dim3((unsigned)p->batch), dim3(sipamd::kkt::TPB),
-                       sizeof(double) * (size_t)th * th, s, p->meta, p->theta_meta, d_theta, d_r1, t.J, t.KJ, t.S,
+                       kkt::lds_bytes(kkt::theta_schur_lds(th)), s, p->meta, p->theta_meta, d_theta, d_r1, t.J, t.KJ,
+                       t.S,
                        d_status, (long)p->batch, (int)SIP_KKT_THETA_SCHUR_FAILURE);
   return report(hipGetLastError(), "sip_kkt_factor_theta(schur)");
 }
@@ -1288,17 +1264,18 @@ int sip_kkt_solve_theta(const sip_kkt_plan *p, const double *d_model, const doub
     return rc;
   if (p->chain_theta) {
     double *d_part = t.J + (size_t)p->batch * p->N * th * th; // behind the Schur partials (kept: solve after solve)
-    hipLaunchKernelGGL(p->k->theta_dot, dim3(node_grid(p)), dim3(sipamd::kkt::TPB), p->lds_theta_dot, s, p->ck, p->ct,
-                       d_theta, (const double *)t.sol_sw, d_part, d_status, (long)p->batch);
+    hipLaunchKernelGGL(p->k->theta_dot, dim3(node_grid(p)), dim3(sipamd::kkt::TPB),
+                       kkt::lds_bytes(kkt::theta_dot_lds(p->ck, p->ct)), s, p->ck, p->ct, d_theta,
+                       (const double *)t.sol_sw, d_part, d_status, (long)p->batch);
     hipLaunchKernelGGL(sipamd::kkt::theta_finish_parts_kernel, dim3((unsigned)p->batch), dim3(sipamd::kkt::TPB),
-                       sizeof(double) * (size_t)th, s, p->N, th, sx, skkt, d_b, (const double *)d_part,
+                       kkt::lds_bytes(kkt::theta_finish_lds(th)), s, p->N, th, sx, skkt, d_b, (const double *)d_part,
                        (const double *)t.KJ, (const double *)t.S, (const double *)t.sol_sw, d_sol, d_status,
                        (long)p->batch);
     return report(hipGetLastError(), "sip_kkt_solve_theta(finish)");
   }
   hipLaunchKernelGGL(sipamd::kkt::theta_finish_kernel, dim3((unsigned)p->batch), dim3(sipamd::kkt::TPB),
-                     sizeof(double) * (size_t)th, s, p->meta, p->theta_meta, d_b, t.J, t.KJ, t.S, t.sol_sw, d_sol,
-                     d_status, (long)p->batch);
+                     kkt::lds_bytes(kkt::theta_finish_lds(th)), s, p->meta, p->theta_meta, d_b, t.J, t.KJ, t.S,
+                     t.sol_sw, d_sol, d_status, (long)p->batch);
   return report(hipGetLastError(), "sip_kkt_solve_theta(finish)");
 }
 
