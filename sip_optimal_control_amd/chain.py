@@ -107,7 +107,7 @@ class BatchedChainLQR:
         = A | B per stage.  A test / demo helper: callers of the split entry point have A | B elsewhere already."""
         s = self.shape
         n, m, T = s.n, s.m, s.T
-        node, edge, abn = n * n + n, n * n + 2 * n * m + m * m, n * n + n * m
+        node, edge, abn = s.node, s.edge, n * n + n * m  # (Q, R packed triangles in the symmetric layout)
         stg = node + edge
         body = mats[:, :T * stg].reshape(self.batch, T, stg)
         qmr = torch.cat([torch.cat([body[:, :, :node], body[:, :, node + abn:]], dim=2).reshape(self.batch, -1),
