@@ -140,6 +140,15 @@ const char *sip_kkt_kernel_name(const sip_kkt_plan *plan);
  * changes nothing.  SIP_LQR_ERR_INVALID_ARGUMENT: NULL plan, or called after sip_kkt_plan_set_theta or a second
  * time with on = 1. */
 int sip_kkt_plan_set_tree_fused(sip_kkt_plan *plan, int on);
+/* Opt-in (on = 1): on a valid uniform-chain plan whose Riccati plan runs the n = 32 matrix-core kernel (16 < n <= 32,
+ * m <= 8), sip_lqr_plan_set_separate_sweeps is applied to that plan: the Riccati part of sip_kkt_factor, sip_kkt_solve,
+ * the factor of sip_kkt_factor_theta and the solves of sip_kkt_solve_theta run the separate factor and solve sweeps,
+ * and the p columns of K^-1 J_theta go through one sweep per 16 columns (exact (32, 4) and (32, 8) shapes).  The kernel
+ * name gains the suffix of sip_lqr_kernel_name.  The rules of sip_kkt_plan_set_tree_fused: call once, right after
+ * sip_kkt_plan_create, before sip_kkt_work_bytes is read and before sip_kkt_plan_set_theta; on other plans it returns
+ * SIP_LQR_OK and changes nothing; on = 0 changes nothing.  SIP_LQR_ERR_INVALID_ARGUMENT: NULL plan, or called after
+ * sip_kkt_plan_set_theta or a second time with on = 1. */
+int sip_kkt_plan_set_chain_separate_sweeps(sip_kkt_plan *plan, int on);
 
 /* Replaces CallbackProvider::factor (helpers.cpp:242-370): checks and inverts
  * the regularization, condenses the constraint Jacobians into Q_mod / M_mod /

@@ -126,6 +126,23 @@ int sip_lqr_plan_layout(const sip_lqr_plan *plan);
 
 void sip_lqr_plan_destroy(sip_lqr_plan *plan);
 
+/* Opt-in (on = 1), on a plan whose kernel is chain_factor_solve_mt16 (exact (32,4) and (32,8) in fp32 and fp64; in
+ * fp64 also the embeddings of 16 < n < 32 / other m <= 8 -- an fp32 plan of such a shape runs on the general engine and
+ * the call changes nothing on it; not with SIP_LQR_SPLIT=general): sip_lqr_factor runs the backward
+ * matrix sweep alone and keeps the factor state (W per node, K, -G^-1 per edge, the statuses), sip_lqr_solve a
+ * vector-only sweep + rollout against it, sip_lqr_solve_multi up to 16 columns per sweep on the matrix cores.
+ * sip_lqr_kernel_name gains the suffix " + chain_factor_mt16 + chain_solve_mt16"; sip_lqr_workspace_bytes does not
+ * shrink; on the exact shapes sip_lqr_solve_multi_workspace_bytes becomes > 0 (g | k per node and column), on embedded
+ * shapes it stays 0 and sip_lqr_solve_multi runs the new single-column solve per column.  sip_lqr_factor_solve is
+ * unaffected.  The factor sweep scales F = I + D^1/2 V D^1/2 to a unit diagonal before it factors it, which the fused
+ * sweep does not: K from sip_lqr_factor on an opt-in plan agrees with K from sip_lqr_factor_solve on the same plan to
+ * rounding (and is the more accurate one on badly scaled problems), NOT bitwise.  sip_lqr_solve and
+ * sip_lqr_solve_multi leave `sol` of a problem whose factorization failed untouched, on exact and embedded shapes.
+ * Call once, right after plan creation, before any size is read.  Other plans: SIP_LQR_OK, nothing changes.
+ * on = 0: nothing changes.  SIP_LQR_ERR_INVALID_ARGUMENT: NULL plan, or a second call with on = 1. */
+int sip_lqr_plan_set_separate_sweeps(sip_lqr_plan *plan, int on);
+int sip_lqr_has_separate_sweeps(const sip_lqr_plan *plan); /* 1 after a successful opt-in that took effect */
+
 /* Sizes, in bytes, of the whole-batch buffers.  Replace
  * LQR::Workspace::num_bytes / LQR::Output::num_bytes (lqr.hpp:104-106,
  * 146-186); size_t, not int (the reference's int overflows at batch

@@ -94,6 +94,9 @@ _SIGNATURES = {
     "sip_kkt_add_Kx_to_y": (ctypes.c_int, [_P] * 9),
     "sip_kkt_plan_set_theta": (ctypes.c_int, [_P, ctypes.c_int]),
     "sip_kkt_plan_set_tree_fused": (ctypes.c_int, [_P, ctypes.c_int]),
+    "sip_kkt_plan_set_chain_separate_sweeps": (ctypes.c_int, [_P, ctypes.c_int]),
+    "sip_lqr_plan_set_separate_sweeps": (ctypes.c_int, [_P, ctypes.c_int]),
+    "sip_lqr_has_separate_sweeps": (ctypes.c_int, [_P]),
     "sip_kkt_theta_len": (ctypes.c_size_t, [_P]),
     "sip_kkt_theta_offset": (ctypes.c_size_t, [_P, ctypes.c_int, ctypes.c_int]),
     "sip_kkt_theta_work_bytes": (ctypes.c_size_t, [_P]),

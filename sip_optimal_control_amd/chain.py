@@ -36,8 +36,11 @@ def _check(code, what):
 class BatchedChainLQR:
     """`batch` independent chain problems of horizon T, state dim n, control dim m."""
 
-    def __init__(self, n, m, T, batch, dtype=torch.float64, device="cuda:0", symmetric=False):
-        """symmetric=True: `mats` in SIP_LQR_LAYOUT_SYMMETRIC (Q, R as packed lower triangles; ChainShape.pack_index
+    def __init__(self, n, m, T, batch, dtype=torch.float64, device="cuda:0", symmetric=False, separate_sweeps=False):
+        """separate_sweeps=True: on plans of the n = 32 matrix-core kernel (16 < n <= 32, m <= 8), factor() runs the
+        matrix sweep alone, solve() a vector-only sweep against it and solve_multi() up to 16 columns per sweep
+        (sip_lqr_plan_set_separate_sweeps; a no-op on other plans, see `has_separate_sweeps`).
+        symmetric=True: `mats` in SIP_LQR_LAYOUT_SYMMETRIC (Q, R as packed lower triangles; ChainShape.pack_index
         converts a full-layout batch); raises for shapes without a symmetric-packed kernel."""
         self._lib = load_library()
         self.shape = ChainShape(n, m, T, symmetric=bool(symmetric))
@@ -49,6 +52,8 @@ class BatchedChainLQR:
                                                     1 if symmetric else 0, ctypes.byref(handle)),
                f"sip_lqr_plan_create_layout(n={n}, m={m}, T={T}, {dtype}, symmetric={bool(symmetric)})")
         self._plan = handle
+        if separate_sweeps:  # before any size is read
+            _check(self._lib.sip_lqr_plan_set_separate_sweeps(handle, 1), "sip_lqr_plan_set_separate_sweeps")
         esize = torch.empty((), dtype=dtype).element_size()
         assert self._lib.sip_lqr_mats_len(handle) == self.shape.mats_len
         assert self._lib.sip_lqr_vecs_len(handle) == self.shape.vecs_len
@@ -60,6 +65,11 @@ class BatchedChainLQR:
     @property
     def kernel_name(self):
         return self._lib.sip_lqr_kernel_name(self._plan).decode()
+
+    @property
+    def has_separate_sweeps(self):
+        """True when the separate_sweeps opt-in took effect on this plan."""
+        return bool(self._lib.sip_lqr_has_separate_sweeps(self._plan))
 
     def empty_sol(self):
         return torch.empty(self.batch, self.shape.vecs_len, dtype=self.dtype, device=self.device)
@@ -176,7 +186,8 @@ class BatchedChainLQR:
     def solve_multi(self, mats, vecs_cols, gains, sol_cols=None, stream=None):
         """LQR::solve() for several right-hand sides against the last factor() (the multi-rhs block of
         solve_stagewise_kkt_matrix, helpers.cpp:521-665): vecs_cols / sol_cols are [num_rhs, batch,
-        vecs_len].  One sweep per 8 columns where the shape has the multi-rhs kernel."""
+        vecs_len].  One sweep per 8 columns where the shape has the multi-rhs kernel (per 16 on the n = 32
+        plans with separate_sweeps)."""
         s = self.shape
         num_rhs = vecs_cols.shape[0]
         if sol_cols is None:

@@ -38,6 +38,16 @@ typedef hipError_t (*launch_split_t)(long batch, int T, const void *mats, const 
                                      long ab_sstride, const void *vecs, void *sol, void *gains, int32_t *status,
                                      void *ws, hipStream_t stream);
 
+// The separate sweeps of the n = 32 matrix-core kernels (sip_lqr_plan_set_separate_sweeps; mt16_launch.hpp).
+// Factor sweep: W per node to `ws`, K to `gains`, -G^-1 per edge to `gfac` (M * M + M scalars per edge), the statuses.
+typedef hipError_t (*launch_factor_sweep_t)(long batch, int T, const void *mats, void *gains, int32_t *status, void *ws,
+                                            void *gfac, hipStream_t stream);
+// Solve sweep for 1 <= ncols <= 16 right-hand sides `col_stride` scalars apart.  cws != nullptr: g and k of the columns
+// go through the column workspace; cws == nullptr (ncols == 1): through the spill and the k part of `gains`.
+typedef hipError_t (*launch_solve_sweep_t)(long batch, int T, const void *mats, const void *vecs_cols, void *sol_cols,
+                                           void *gains, void *ws, const void *gfac, void *cws, const int32_t *status,
+                                           int ncols, long col_stride, hipStream_t stream);
+
 struct KernelEntry {
   int dtype, n, m;
   const char *name;
@@ -47,6 +57,9 @@ struct KernelEntry {
   int layout;                  // SIP_LQR_LAYOUT_* of mats the kernel reads (0: the full squares)
   bool core;                   // a slice entry that SIP_LQR_EXTRA=0 leaves visible
   launch_split_t launch_split; // nullptr: no split form of this kernel
+  // both nullptr: the kernel has no separate factor / solve sweeps to opt into
+  launch_factor_sweep_t launch_factor_sweep = nullptr;
+  launch_solve_sweep_t launch_solve_sweep = nullptr;
 };
 
 // slice s of qw16_kernels.hip defines qw16_slice_<s>: its share of the manifest's entries

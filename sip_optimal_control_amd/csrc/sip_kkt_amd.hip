@@ -770,6 +770,27 @@ int sip_kkt_plan_set_tree_fused(sip_kkt_plan *p, int on) {
   return SIP_LQR_OK;
 }
 
+int sip_kkt_plan_set_chain_separate_sweeps(sip_kkt_plan *p, int on) {
+  if (p == nullptr || p->theta_dim != 0 || (on && p->chain != nullptr && sip_lqr_has_separate_sweeps(p->chain)))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  if (!on || p->input_status != SIP_KKT_SUCCESS || p->chain == nullptr)
+    return SIP_LQR_OK; // tree plans: nothing to switch
+  const std::string before = sip_lqr_kernel_name(p->chain);
+  const size_t lqr_bytes = sip_lqr_workspace_bytes(p->chain);
+  const int rc = sip_lqr_plan_set_separate_sweeps(p->chain, 1);
+  if (rc != SIP_LQR_OK || !sip_lqr_has_separate_sweeps(p->chain))
+    return rc; // not a plan of the n = 32 matrix-core kernel: nothing changed
+  // (the Riccati workspace of such a plan already holds what the separate sweeps keep; should it ever grow, the
+  // arena, which ends d_work, grows with it)
+  const size_t now = sip_lqr_workspace_bytes(p->chain);
+  if (now > lqr_bytes)
+    p->work_bytes = align256(p->at_lqr + now);
+  const std::string head = "chain:" + before;
+  const std::string rest = p->name.compare(0, head.size(), head) == 0 ? p->name.substr(head.size()) : "";
+  p->name = std::string("chain:") + sip_lqr_kernel_name(p->chain) + rest;
+  return SIP_LQR_OK;
+}
+
 int sip_kkt_factor(const sip_kkt_plan *p, const double *d_model, const double *d_w, const double *d_r1,
                    const double *d_r2, const double *d_r3, void *d_work, int32_t *d_status, void *stream) {
   if (p == nullptr || d_status == nullptr)

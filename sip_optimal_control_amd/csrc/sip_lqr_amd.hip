@@ -52,7 +52,12 @@ struct sip_lqr_plan {
   // device-side repack before and after the sweep.  SIP_LQR_PAD=0 keeps the general engine.
   bool padded = false;
   int kn = 0, km = 0;
-  bool solve_only = false; // the kernel has the vector-only solve mode (qw16)
+  bool solve_only = false; // the kernel has the vector-only solve mode (qw16; mt16 with the separate sweeps)
+  // sip_lqr_plan_set_separate_sweeps on a plan whose kernel row has them: factor and solve as sweeps of their own
+  // (chain_factor_mt16, chain_solve_mt16); `separate` until then false, the launchers are the row's
+  bool separate = false;
+  sipamd::launch_factor_sweep_t launch_factor_sep = nullptr;
+  sipamd::launch_solve_sweep_t launch_solve_sep = nullptr;
   std::string name_storage;
 };
 
@@ -92,6 +97,7 @@ const KernelEntry kKernels[] = {
     MT16_ENTRY(SIP_LQR_F64, double, "f64", 8), MT16_ENTRY(SIP_LQR_F64, double, "f64", 4),
     MF32(8),
 };
+const char kSeparateSuffix[] = " + chain_factor_mt16 + chain_solve_mt16";
 
 // kKernels, then the fused fp64 kernels of every shape n <= 16, m <= 8 (the slices of qw16_kernels.hip, where
 // the alternatives of a shape stand together, the default first).  SIP_LQR_EXTRA=0 (tests of the embedding)
@@ -245,14 +251,18 @@ pad_mats_kernel(const PadDims d, const double *__restrict__ mats, double *__rest
 }
 
 // vecs -> padded vecs (zeros on the extras); PAD = false: padded sol -> sol
+// (skip != nullptr: problems with skip[problem] != 0 are left alone -- the solve sweep wrote nothing for them)
 template <bool PAD>
 __global__ void __launch_bounds__(256)
-pad_vecs_kernel(const PadDims d, const double *__restrict__ src_all, double *__restrict__ dst_all, long batch) {
+pad_vecs_kernel(const PadDims d, const double *__restrict__ src_all, double *__restrict__ dst_all, long batch,
+                const int32_t *__restrict__ skip = nullptr) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long len = PAD ? d.pvecs_len : d.vecs_len;
   if (idx >= batch * len)
     return;
   const long prob = idx / len;
+  if (skip != nullptr && skip[prob] != 0)
+    return;
   long at = idx - prob * len;
   const int n = d.n, m = d.m, N = d.N, M = d.M;
   const int a = PAD ? N : n, b = PAD ? M : m;   // dims of the layout this thread indexes
@@ -315,7 +325,8 @@ FusedSplit fused_split_layout(const sip_lqr_plan *p) {
 // The sweep of a plan, through the embedding when the plan is padded.  mode 0: fused factor + solve;
 // 1: split factor (vecs == nullptr: zero right-hand side; sol not wanted); 2: split solve against
 // the state a mode-1 call left in `ws` (and, unpadded, in `gains`); kernels without a solve-only
-// mode run the full sweep instead.
+// mode run the full sweep instead.  A plan with the separate sweeps runs its factor sweep in mode 1 and its solve
+// sweep (one column; g and k through the spill and the gains) in mode 2.
 hipError_t run_fused(const sip_lqr_plan *p, const void *mats, const void *vecs, void *sol, void *gains,
                      int32_t *status, void *ws, hipStream_t s, int mode) {
   const FusedSplit f = fused_split_layout(p);
@@ -323,14 +334,22 @@ hipError_t run_fused(const sip_lqr_plan *p, const void *mats, const void *vecs, 
   hipError_t e = hipSuccess;
   if (mode == 2 && !p->solve_only)
     mode = 0;
+  const bool factor_sweep = p->separate && mode == 1; // reads no right-hand side
+  auto sweep = [&](const void *km, const void *kv, void *ksol, void *kgains) {
+    if (factor_sweep)
+      return p->launch_factor_sep(p->batch, p->T, km, kgains, status, ws, w + f.gfac, s);
+    if (p->separate && mode == 2)
+      return p->launch_solve_sep(p->batch, p->T, km, kv, ksol, kgains, ws, w + f.gfac, nullptr, status, 1, 0L, s);
+    return p->launch_fs(p->batch, p->T, km, kv, ksol, kgains, status, ws, s, mode, w + f.gfac);
+  };
   if (!p->padded) {
     const void *v = vecs;
-    if (v == nullptr) {
+    if (v == nullptr && !factor_sweep) {
       e = sipamd::zero_async(w + f.vecs, f.sol - f.vecs, s);
       v = w + f.vecs;
     }
     if (e == hipSuccess)
-      e = p->launch_fs(p->batch, p->T, mats, v, sol ? sol : (void *)(w + f.sol), gains, status, ws, s, mode, w + f.gfac);
+      e = sweep(mats, v, sol ? sol : (void *)(w + f.sol), gains);
     return e;
   }
   const PadDims d = pad_dims(p);
@@ -341,14 +360,14 @@ hipError_t run_fused(const sip_lqr_plan *p, const void *mats, const void *vecs, 
                        d, (const double *)mats, (double *)(w + f.pmats), B);
   if (vecs != nullptr)
     hipLaunchKernelGGL(pad_vecs_kernel<true>, grid(B * d.pvecs_len), dim3(256), 0, s, d, (const double *)vecs,
-                       (double *)(w + f.vecs), B);
-  else
+                       (double *)(w + f.vecs), B, (const int32_t *)nullptr);
+  else if (!factor_sweep)
     e = sipamd::zero_async(w + f.vecs, f.sol - f.vecs, s);
   if (e == hipSuccess)
-    e = p->launch_fs(p->batch, p->T, w + f.pmats, w + f.vecs, w + f.sol, w + f.pgains, status, ws, s, mode, w + f.gfac);
+    e = sweep(w + f.pmats, w + f.vecs, w + f.sol, w + f.pgains);
   if (e == hipSuccess && sol != nullptr)
     hipLaunchKernelGGL(pad_vecs_kernel<false>, grid(B * d.vecs_len), dim3(256), 0, s, d, (const double *)(w + f.sol),
-                       (double *)sol, B);
+                       (double *)sol, B, (const int32_t *)(p->separate && mode == 2 ? status : nullptr));
   if (e == hipSuccess && gains != nullptr && d.gains_len > 0)
     hipLaunchKernelGGL(unpad_gains_kernel, grid(B * d.gains_len), dim3(256), 0, s, d,
                        (const double *)(w + f.pgains), (double *)gains, B);
@@ -413,6 +432,8 @@ int sip_lqr_plan_create_layout(int dtype, int64_t batch, int T, int n, int m, in
                    : k       ? k->name
                              : (dtype == SIP_LQR_F32 ? "tree_generic(chain layout)/f32"
                                                      : "tree_generic(chain layout)/f64");
+  p->launch_factor_sep = k ? k->launch_factor_sweep : nullptr;
+  p->launch_solve_sep = k ? k->launch_solve_sweep : nullptr;
   p->ws_slot = k ? k->ws_slot : 0;
   p->launch_fs = k ? k->launch_fs : nullptr;
   p->launch_mrhs = (k != nullptr && !p->padded) ? k->launch_mrhs : nullptr;
@@ -447,6 +468,23 @@ int sip_lqr_plan_create_layout(int dtype, int64_t batch, int T, int n, int m, in
 }
 
 void sip_lqr_plan_destroy(sip_lqr_plan *plan) { delete plan; }
+
+int sip_lqr_plan_set_separate_sweeps(sip_lqr_plan *plan, int on) {
+  if (plan == nullptr || (on && plan->separate))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  if (!on || plan->launch_factor_sep == nullptr || plan->launch_solve_sep == nullptr || !plan->split_on_fused)
+    return SIP_LQR_OK; // the plan's kernel has no such sweeps (or its split calls run on the general engine)
+  plan->separate = true;
+  plan->solve_only = true;
+  // the workspace stays what it was: the spill, the scratch of the split calls and the gfac region (-G^-1 per edge)
+  // are those fused_split_layout already reserves
+  std::string name = std::string(plan->kernel_name) + kSeparateSuffix;
+  plan->name_storage.swap(name);
+  plan->kernel_name = plan->name_storage.c_str();
+  return SIP_LQR_OK;
+}
+
+int sip_lqr_has_separate_sweeps(const sip_lqr_plan *plan) { return plan != nullptr && plan->separate ? 1 : 0; }
 
 int64_t sip_lqr_plan_batch(const sip_lqr_plan *p) { return p ? p->batch : 0; }
 size_t sip_lqr_scalar_bytes(const sip_lqr_plan *p) { return p ? scalar_size(p) : 0; }
@@ -729,6 +767,9 @@ int sip_lqr_solve(const sip_lqr_plan *plan, const void *d_mats, const void *d_ve
 }
 
 size_t sip_lqr_solve_multi_workspace_bytes(const sip_lqr_plan *plan, int num_rhs) {
+  if (plan != nullptr && num_rhs >= 1 && plan->separate && !plan->padded) // g | k per node and column of a sweep
+    return (size_t)plan->batch * scalar_size(plan) *
+           (size_t)sipamd::mt16_col_workspace_scalars(plan->T, plan->km, std::min(num_rhs, sipamd::kMt16SolveColumns));
   if (plan == nullptr || num_rhs < 1 || plan->launch_mrhs == nullptr || !plan->split_on_fused)
     return 0; // column-by-column path: no extra state
   const int cols = std::min(num_rhs, sipamd::kMrhsColumns);
@@ -741,6 +782,26 @@ int sip_lqr_solve_multi(const sip_lqr_plan *plan, const void *d_mats, const void
       (num_rhs > 0 && (!d_vecs_cols || !d_sol_cols)))
     return SIP_LQR_ERR_INVALID_ARGUMENT;
   const size_t col_bytes = sip_lqr_vecs_bytes(plan);
+  if (plan->separate && !plan->padded) { // the solve sweep of the n = 32 kernel: up to 16 columns per launch
+    if (num_rhs > 0 && d_col_workspace == nullptr)
+      return SIP_LQR_ERR_INVALID_ARGUMENT;
+    if (require_device(plan) != hipSuccess)
+      return report(hipErrorNoDevice, "sip_lqr_solve_multi");
+    sipamd::DeviceGuard on_device(plan->device);
+    if (on_device.err != hipSuccess)
+      return report(on_device.err, "sip_lqr_solve_multi(hipSetDevice)");
+    const FusedSplit f = fused_split_layout(plan);
+    char *w = (char *)d_workspace;
+    const long stride = (long)(col_bytes / scalar_size(plan));
+    hipError_t e = hipSuccess;
+    for (int col0 = 0; col0 < num_rhs && e == hipSuccess; col0 += sipamd::kMt16SolveColumns) {
+      const int nc = std::min(sipamd::kMt16SolveColumns, num_rhs - col0);
+      e = plan->launch_solve_sep(plan->batch, plan->T, d_mats, (const char *)d_vecs_cols + (size_t)col0 * col_bytes,
+                                 (char *)d_sol_cols + (size_t)col0 * col_bytes, d_gains, d_workspace, w + f.gfac,
+                                 d_col_workspace, (const int32_t *)(w + f.status), nc, stride, (hipStream_t)stream);
+    }
+    return report(e, "sip_lqr_solve_multi(mt16)");
+  }
   if (plan->launch_mrhs == nullptr || !plan->split_on_fused) { // no multi-rhs kernel for this shape
     for (int col = 0; col < num_rhs; ++col) {
       const int rc = sip_lqr_solve(plan, d_mats, (const char *)d_vecs_cols + (size_t)col * col_bytes,
