@@ -143,6 +143,22 @@ void sip_lqr_plan_destroy(sip_lqr_plan *plan);
 int sip_lqr_plan_set_separate_sweeps(sip_lqr_plan *plan, int on);
 int sip_lqr_has_separate_sweeps(const sip_lqr_plan *plan); /* 1 after a successful opt-in that took effect */
 
+/* Opt-in (on = 1), on an fp32 FULL-layout plan that runs on the general engine and whose (n, m) has a row in the table
+ * of the fused fp32 kernel chain_factor_solve_qf32 (csrc/chain_qf32.hpp: n <= 15, m <= 8; rows: n in {4, 6, 8, 12} x
+ * m in {1, 2, 3, 4}, and (1, 1), (5, 3), (9, 2), (15, 8)): the plan takes that kernel -- one fused launch, four
+ * problems per wavefront, the arithmetic of the fp64 kernels on `float` -- instead of the general engine's factor and
+ * solve launches.  sip_lqr_kernel_name becomes "chain_factor_solve_qf32<n,m,direct>/f32"; sip_lqr_workspace_bytes
+ * becomes the larger of the fused and the general layout (it does not shrink); the per-problem lengths are unchanged.
+ * sip_lqr_factor, sip_lqr_solve and sip_lqr_solve_multi re-run the full sweep (factor on a zero right-hand side,
+ * solve_multi column by column, sip_lqr_solve_multi_workspace_bytes stays 0), unless SIP_LQR_SPLIT=general keeps them
+ * on the general engine; sip_lqr_solve then computes bitwise what sip_lqr_factor_solve computes.  Statuses are exact;
+ * sol and gains of a problem whose status != SUCCESS are unspecified, as for every fused kernel.
+ * Call once, right after plan creation, before any size is read.  fp64 plans, fp32 plans whose shape has no row
+ * (n = 16 and n = 32 among them), plans created under SIP_LQR_VARIANT=general, and on = 0: SIP_LQR_OK, nothing
+ * changes.  SIP_LQR_ERR_INVALID_ARGUMENT: NULL plan, or a second call with on = 1 after one that took effect. */
+int sip_lqr_plan_set_fused_f32(sip_lqr_plan *plan, int on);
+int sip_lqr_has_fused_f32(const sip_lqr_plan *plan); /* 1 after an opt-in that took effect */
+
 /* Sizes, in bytes, of the whole-batch buffers.  Replace
  * LQR::Workspace::num_bytes / LQR::Output::num_bytes (lqr.hpp:104-106,
  * 146-186); size_t, not int (the reference's int overflows at batch

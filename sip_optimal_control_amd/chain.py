@@ -36,10 +36,14 @@ def _check(code, what):
 class BatchedChainLQR:
     """`batch` independent chain problems of horizon T, state dim n, control dim m."""
 
-    def __init__(self, n, m, T, batch, dtype=torch.float64, device="cuda:0", symmetric=False, separate_sweeps=False):
+    def __init__(self, n, m, T, batch, dtype=torch.float64, device="cuda:0", symmetric=False, separate_sweeps=False,
+                 fused_f32=False):
         """separate_sweeps=True: on plans of the n = 32 matrix-core kernel (16 < n <= 32, m <= 8), factor() runs the
         matrix sweep alone, solve() a vector-only sweep against it and solve_multi() up to 16 columns per sweep
         (sip_lqr_plan_set_separate_sweeps; a no-op on other plans, see `has_separate_sweeps`).
+        fused_f32=True: an fp32 plan whose (n, m) has a fused fp32 kernel (n <= 15, m <= 8: the benchmark grid
+        n in {4, 6, 8, 12} x m in {1, 2, 3, 4} and a few more) runs on it instead of the general engine
+        (sip_lqr_plan_set_fused_f32; a no-op on other plans, see `has_fused_f32`).
         symmetric=True: `mats` in SIP_LQR_LAYOUT_SYMMETRIC (Q, R as packed lower triangles; ChainShape.pack_index
         converts a full-layout batch); raises for shapes without a symmetric-packed kernel."""
         self._lib = load_library()
@@ -54,6 +58,8 @@ class BatchedChainLQR:
         self._plan = handle
         if separate_sweeps:  # before any size is read
             _check(self._lib.sip_lqr_plan_set_separate_sweeps(handle, 1), "sip_lqr_plan_set_separate_sweeps")
+        if fused_f32:  # likewise
+            _check(self._lib.sip_lqr_plan_set_fused_f32(handle, 1), "sip_lqr_plan_set_fused_f32")
         esize = torch.empty((), dtype=dtype).element_size()
         assert self._lib.sip_lqr_mats_len(handle) == self.shape.mats_len
         assert self._lib.sip_lqr_vecs_len(handle) == self.shape.vecs_len
@@ -70,6 +76,11 @@ class BatchedChainLQR:
     def has_separate_sweeps(self):
         """True when the separate_sweeps opt-in took effect on this plan."""
         return bool(self._lib.sip_lqr_has_separate_sweeps(self._plan))
+
+    @property
+    def has_fused_f32(self):
+        """True when the fused_f32 opt-in took effect on this plan."""
+        return bool(self._lib.sip_lqr_has_fused_f32(self._plan))
 
     def empty_sol(self):
         return torch.empty(self.batch, self.shape.vecs_len, dtype=self.dtype, device=self.device)

@@ -16,6 +16,7 @@
 
 #include "chain_mf32.hpp"
 #include "mt16_launch.hpp"
+#include "qf32_launch.hpp"
 #include "generic_plan.hpp"
 #include "qw16_table.hpp"
 #include "stream_fill.hpp"
@@ -58,6 +59,10 @@ struct sip_lqr_plan {
   bool separate = false;
   sipamd::launch_factor_sweep_t launch_factor_sep = nullptr;
   sipamd::launch_solve_sweep_t launch_solve_sep = nullptr;
+  // sip_lqr_plan_set_fused_f32 on an fp32 plan of the general engine whose shape has a row in kQf32Rows: the plan
+  // runs on chain_factor_solve_qf32.  forced_general: SIP_LQR_VARIANT=general at creation, which the opt-in respects
+  bool fused_f32 = false;
+  bool forced_general = false;
   std::string name_storage;
 };
 
@@ -98,6 +103,10 @@ const KernelEntry kKernels[] = {
     MF32(8),
 };
 const char kSeparateSuffix[] = " + chain_factor_mt16 + chain_solve_mt16";
+
+// fp32, n <= 15: four problems per wavefront on v_fmac_f32_dpp (chain_qf32.hpp).  A table of its own that find_kernel
+// never searches: a plan gets one of these rows through sip_lqr_plan_set_fused_f32 alone.
+const KernelEntry kQf32Rows[] = {SIP_QF32_ROWS(QF32_ENTRY)};
 
 // kKernels, then the fused fp64 kernels of every shape n <= 16, m <= 8 (the slices of qw16_kernels.hip, where
 // the alternatives of a shape stand together, the default first).  SIP_LQR_EXTRA=0 (tests of the embedding)
@@ -418,6 +427,7 @@ int sip_lqr_plan_create_layout(int dtype, int64_t batch, int T, int n, int m, in
   p->n = n;
   p->m = m;
   p->device = device;
+  p->forced_general = force_general;
   p->kn = n, p->km = m;
   const char *pad = std::getenv("SIP_LQR_PAD");
   if (k == nullptr && !force_general && dtype == SIP_LQR_F64 && (want == nullptr || want[0] == 0) &&
@@ -485,6 +495,31 @@ int sip_lqr_plan_set_separate_sweeps(sip_lqr_plan *plan, int on) {
 }
 
 int sip_lqr_has_separate_sweeps(const sip_lqr_plan *plan) { return plan != nullptr && plan->separate ? 1 : 0; }
+
+int sip_lqr_plan_set_fused_f32(sip_lqr_plan *plan, int on) {
+  if (plan == nullptr || (on && plan->fused_f32))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  if (!on || plan->dtype != SIP_LQR_F32 || plan->layout != SIP_LQR_LAYOUT_FULL || plan->launch_fs != nullptr ||
+      plan->forced_general)
+    return SIP_LQR_OK; // not an fp32 plan of the general engine, or one that was asked to stay there
+  const KernelEntry *row = nullptr;
+  for (const KernelEntry &k : kQf32Rows)
+    if (row == nullptr && k.n == plan->n && k.m == plan->m)
+      row = &k;
+  if (row == nullptr)
+    return SIP_LQR_OK; // no fused fp32 kernel of this shape
+  plan->fused_f32 = true;
+  plan->kernel_name = row->name;
+  plan->ws_slot = row->ws_slot;
+  plan->launch_fs = row->launch_fs;
+  // factor and solve re-run the sweep (solve_only stays false), unless the split calls were asked to stay general;
+  // sip_lqr_workspace_bytes is the larger of the two layouts from here on, as for every fused plan
+  const char *split = std::getenv("SIP_LQR_SPLIT");
+  plan->split_on_fused = !(split && std::strcmp(split, "general") == 0);
+  return SIP_LQR_OK;
+}
+
+int sip_lqr_has_fused_f32(const sip_lqr_plan *plan) { return plan != nullptr && plan->fused_f32 ? 1 : 0; }
 
 int64_t sip_lqr_plan_batch(const sip_lqr_plan *p) { return p ? p->batch : 0; }
 size_t sip_lqr_scalar_bytes(const sip_lqr_plan *p) { return p ? scalar_size(p) : 0; }
