@@ -134,9 +134,9 @@ void sip_lqr_plan_destroy(sip_lqr_plan *plan);
  * sip_lqr_kernel_name gains the suffix " + chain_factor_mt16 + chain_solve_mt16"; sip_lqr_workspace_bytes does not
  * shrink; on the exact shapes sip_lqr_solve_multi_workspace_bytes becomes > 0 (g | k per node and column), on embedded
  * shapes it stays 0 and sip_lqr_solve_multi runs the new single-column solve per column.  sip_lqr_factor_solve is
- * unaffected.  The factor sweep scales F = I + D^1/2 V D^1/2 to a unit diagonal before it factors it, which the fused
- * sweep does not: K from sip_lqr_factor on an opt-in plan agrees with K from sip_lqr_factor_solve on the same plan to
- * rounding (and is the more accurate one on badly scaled problems), NOT bitwise.  sip_lqr_solve and
+ * unaffected.  The factor sweep scales F = I + D^1/2 V D^1/2 to a unit diagonal before it factors it; the fused
+ * sweep does so in fp64 only: K from sip_lqr_factor on an opt-in plan agrees with K from sip_lqr_factor_solve on the
+ * same plan to rounding (in fp32 it is the more accurate one on badly scaled problems), NOT bitwise.  sip_lqr_solve and
  * sip_lqr_solve_multi leave `sol` of a problem whose factorization failed untouched, on exact and embedded shapes.
  * Call once, right after plan creation, before any size is read.  Other plans: SIP_LQR_OK, nothing changes.
  * on = 0: nothing changes.  SIP_LQR_ERR_INVALID_ARGUMENT: NULL plan, or a second call with on = 1. */

@@ -126,12 +126,14 @@
           }
     }
     SIP_MT16_STAMP(8);
-    // The factor sweep alone sweeps the unit-diagonal S F S, S = diag(F)^-1/2, and scales back, as the G sweep below
-    // does: the sweep's modified operands work against an identity on the pivot block, and the F of a condensed
-    // Newton-KKT problem (V ~ J^T R2^-1 J) has a diagonal far from 1.  (A diagonal <= 0 gives a NaN scale: the sweep
-    // then fails, as it must.)  The fused kernel keeps its sweep of F as it stands.
+    // The factor sweep alone, and the fused sweep in fp64, sweep the unit-diagonal S F S, S = diag(F)^-1/2, and scale
+    // back, as the G sweep below does: the sweep's modified operands work against an identity on the pivot block, and
+    // the F of a condensed Newton-KKT problem (V ~ J^T R2^-1 J) has a diagonal far from 1.  (A diagonal <= 0 gives a
+    // NaN scale: the sweep then fails, as it must.)  The fp32 fused kernel keeps its sweep of F as it stands: its
+    // register allocation is tuned to the last VGPR.
+    constexpr bool SCALE_F = FACTOR || sizeof(S) == 8;
     S fs0 = S(1), fs1 = S(1);
-    if constexpr (FACTOR) {
+    if constexpr (SCALE_F) {
       S d0 = S(0), d1 = S(0);
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
@@ -140,7 +142,7 @@
       }
       fs0 = TR::rsqrt(sum_groups(d0)), fs1 = TR::rsqrt(sum_groups(d1)); // of tile columns j and 16 + j
       if (g == 0)
-        s_x[j] = fs0, s_x[16 + j] = fs1; // (s_x is the rollout's: free here)
+        s_x[j] = fs0, s_x[16 + j] = fs1; // (s_x is the rollout's, first written after the backward sweep: free here)
       lds_order();
       const v4 fr[2] = {by_row<S>(s_x, 0, g), by_row<S>(s_x, 1, g)};
       lds_order();
@@ -162,7 +164,7 @@
       if (stat == 0 && ffail_scaled)
         stat = 2; // F_FACTORIZATION_FAILURE
     }
-    const bool ffail = FACTOR ? false : sweep<S, 2, 4>(V.t, L, s_p); // V now holds -F^-1
+    const bool ffail = SCALE_F ? false : sweep<S, 2, 4>(V.t, L, s_p); // V now holds -F^-1
     SIP_MT16_STAMP(9);
     if (stat == 0 && ffail)
       stat = 2; // F_FACTORIZATION_FAILURE

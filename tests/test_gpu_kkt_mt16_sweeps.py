@@ -2,11 +2,11 @@
 uniform chain whose Riccati plan runs the n = 32 matrix-core kernel, with the separate factor / solve sweeps off and on,
 against KKTOracle; the theta Schur complement (p columns of K^-1 J_theta through sip_lqr_solve_multi) likewise.
 
-The opt-in-off legs at (32, 8, 4) are not here: on these condensed problems the default plan (the fused mt16 sweep, which
-this file does not change) measures 1.85e-9 (factor + solve, problem 2) and 1.2e-8 (theta, problem 2) against the
-oracle, above the 1e-9 asked for, where the general engine measures 3e-15 -- the fused kernel sweeps F = I + D^1/2 V D^1/2
-as it stands, and the F of a condensed problem has a diagonal far from 1.  The factor sweep of the opt-in scales F to
-a unit diagonal first and measures 6e-13 / 1.4e-12 on the same problems.  The off leg at (20, 3, 5) passes (7.9e-10)."""
+Both legs run at (32, 8, 4) and at the embedded (20, 3, 5), at 1e-9.  The F of a condensed problem (V ~ J^T R2^-1 J)
+has a diagonal far from 1, and a sweep of F = I + D^1/2 V D^1/2 as it stands loses six digits on it: before the fused
+fp64 kernel scaled F to a unit diagonal, as the factor sweep of the opt-in always did, the off legs at (32, 8, 4)
+measured 1.85e-9 (factor + solve) and 1.2e-8 (theta) and were left out of this file.  With the scaling the two legs
+measure the same 1e-12."""
 import ctypes
 
 import numpy as np
@@ -38,9 +38,9 @@ def _dev(*arrays):
     return [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda() for a in arrays]
 
 
-@pytest.mark.parametrize("n,m,T,on", [(32, 8, 4, True), (20, 3, 5, False), (20, 3, 5, True)])
+@pytest.mark.parametrize("n,m,T,on", [(32, 8, 4, False), (32, 8, 4, True), (20, 3, 5, False), (20, 3, 5, True)])
 def test_factor_then_two_solves(n, m, T, on):
-    """factor + solve with two right-hand sides within 1e-9 of KKTOracle, the opt-in on (and off at (20, 3, 5))."""
+    """factor + solve with two right-hand sides within 1e-9 of KKTOracle, the opt-in off and on."""
     batch = 3
     dims = rk.newton_kkt_dims(n, m, T)
     arrays = rk.newton_kkt_problem(dims, seed=100 * n + m, batch=batch, r2_max=1e2)
@@ -60,15 +60,15 @@ def test_factor_then_two_solves(n, m, T, on):
         assert err <= REL, err
 
 
-def test_theta_schur_complement():
-    """(32, 8, 4) with p = 3: factor_theta (the 3 columns of K^-1 J_theta) + solve_theta within 1e-9 of the oracle."""
+def _theta_schur_complement(on):
     n, m, T, p, batch = 32, 8, 4, 3, 3
     base = rk.newton_kkt_dims(n, m, T)
     dims = rk.KKTDims(base.parents, base.children, base.sd, base.cd, base.ncd, base.ngd, base.ecd, base.egd,
                       theta_dim=p)
     model, w, r1, r2, r3, rhs, theta_model = rk.newton_kkt_problem(dims, seed=7 + n, batch=batch, r2_max=1e2)
-    kkt = _make(dims, batch, True)
-    assert SUFFIX in kkt.kernel_name, kkt.kernel_name
+    kkt = _make(dims, batch, on)
+    assert kkt.kernel_name.startswith("chain:chain_factor_solve_mt16<32,8,") and (SUFFIX in kkt.kernel_name) == on, \
+        kkt.kernel_name
     d = _dev(model, theta_model, w, r1, r2, r3, rhs)
     assert kkt.factor_theta(*d[:6]).cpu().tolist() == [0] * batch
     sol = kkt.solve_theta(d[0], d[1], d[6]).cpu().numpy()
@@ -79,6 +79,16 @@ def test_theta_schur_complement():
         err = np.abs(sol[q] - ref).max() / np.abs(ref).max()
         print(f"{kkt.kernel_name}: theta, problem {q}: {err:.2e}")
         assert err <= REL, (q, err)
+
+
+def test_theta_schur_complement():
+    """(32, 8, 4) with p = 3: factor_theta (the 3 columns of K^-1 J_theta) + solve_theta within 1e-9 of the oracle."""
+    _theta_schur_complement(True)
+
+
+def test_theta_schur_complement_without_the_opt_in():
+    """The same with the opt-in off: the columns go through the fused sweep one by one."""
+    _theta_schur_complement(False)
 
 
 def _kkt_plan(lib, n, m, horizon=4, batch=3):
