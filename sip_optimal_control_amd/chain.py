@@ -159,7 +159,7 @@ class BatchedChainLQR:
         return sol, gains, self.status
 
     def factor(self, mats, gains=None, stream=None):
-        """LQR::factor_with_status() alone (general engine): statuses, K part of gains,
+        """LQR::factor_with_status() alone (the plan's fused sweep, or the general engine): statuses, K part of gains,
         factor state kept in the workspace for later solve() calls."""
         s = self.shape
         if gains is None:

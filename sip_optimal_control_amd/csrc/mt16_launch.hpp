@@ -7,7 +7,7 @@
 
 namespace sipamd {
 
-// Same signature as launch_fs_t (qw16_launch.hpp); `mode` is ignored: the kernel always runs the full
+// Same signature as launch_fs_t (qw16_table.hpp); `mode` is ignored: the kernel always runs the full
 // sweep (split factor / solve calls re-run it, see sip_lqr_plan::split_on_fused).
 template <typename S, int M>
 hipError_t launch_mt16(long batch, int T, const void *mats, const void *vecs, void *sol, void *gains,
@@ -15,7 +15,7 @@ hipError_t launch_mt16(long batch, int T, const void *mats, const void *vecs, vo
 
 constexpr int kMt16SpillPerNode = 3 * 256 + 32; // Layout::WSN: three tiles of the symmetric W | g
 
-// ---- the separate sweeps (sip_lqr_plan_set_separate_sweeps): launch_factor_sweep_t / launch_solve_sweep_t of
+// ---- the separate sweeps (sip_lqr_plan_set_separate_sweeps): launch_factor_sweep_t / launch_cols_t of
 // qw16_table.hpp, instantiated in chain_mt16_solve.hip (chain_factor_mt16, chain_solve_mt16) ----
 constexpr int kMt16SolveColumns = 16; // the columns of a 16 x 16 tile
 constexpr long mt16_col_workspace_scalars(int T, int m, int ncols) { return (long)(T + 1) * ncols * (32 + m); }
@@ -31,6 +31,6 @@ hipError_t launch_mt16_solve(long batch, int T, const void *mats, const void *ve
 } // namespace sipamd
 
 #define MT16_ENTRY(DT, S, TAG, M)                                                                            \
-  { DT, 32, M, "chain_factor_solve_mt16<32," #M ",mfma16x16x4>/" TAG, sipamd::kMt16SpillPerNode,             \
-    &sipamd::launch_mt16<S, M>, nullptr, 0, false, nullptr,                                                  \
-    &sipamd::launch_mt16_factor<S, M>, &sipamd::launch_mt16_solve<S, M> }
+  sipamd::with_separate_sweeps({DT, 32, M, "chain_factor_solve_mt16<32," #M ",mfma16x16x4>/" TAG,            \
+                                sipamd::kMt16SpillPerNode, &sipamd::launch_mt16<S, M>},                      \
+                               &sipamd::launch_mt16_factor<S, M>, &sipamd::launch_mt16_solve<S, M>)

@@ -45,4 +45,4 @@ hipError_t launch_qf32(long batch, int T, const void *mats, const void *vecs, vo
 // One row of the opt-in table (sip_lqr_plan_set_fused_f32): never part of find_kernel's search.
 #define QF32_ENTRY(N, M)                                                                                     \
   {SIP_LQR_F32, N, M, "chain_factor_solve_qf32<" #N "," #M ",direct>/f32", sipamd::qf32::Layout<N, M>::WSN,   \
-   &sipamd::qf32::launch_qf32<N, M>, nullptr, SIP_LQR_LAYOUT_FULL, false, nullptr},
+   &sipamd::qf32::launch_qf32<N, M>},

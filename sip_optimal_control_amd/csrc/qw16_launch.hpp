@@ -14,8 +14,8 @@ constexpr int kMrhsGroup = SIP_MRHS_GROUP; // columns one wavefront carries of t
 
 template <int N, int M, bool WPACK>
 hipError_t launch_mrhs_qw16(long batch, int T, const void *mats, const void *vecs_cols, void *sol_cols,
-                            const void *gains, const void *ws, const void *gfac, void *cws, const int32_t *status,
-                            int ncols, long col_stride, hipStream_t stream) {
+                            void *gains, void *ws, const void *gfac, void *cws, const int32_t *status, int ncols,
+                            long col_stride, hipStream_t stream) {
   if (ncols < 1 || ncols > kMrhsColumns)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL((chain_solve_mrhs_qw16<N, M, WPACK, kMrhsGroup>),
@@ -75,5 +75,5 @@ hipError_t launch_qw16_split(long batch, int T, const void *mats, const void *ab
 #define QW16_ENTRY(N, M, STAGED, SYM, TAG, CORE, MRHS, SPLIT)                                                  \
   { SIP_LQR_F64, N, M, "chain_factor_solve_qw16<" #N "," #M "," TAG ">/f64",                                   \
     sipamd::StagedCfg<N, M, STAGED, false, SYM>::WSN, &sipamd::launch_qw16<N, M, STAGED, STAGED, SYM>,         \
-    MRHS(N, M, STAGED, SYM), SYM ? SIP_LQR_LAYOUT_SYMMETRIC : SIP_LQR_LAYOUT_FULL, CORE,                       \
-    SPLIT(N, M, STAGED, SYM) }
+    SYM ? SIP_LQR_LAYOUT_SYMMETRIC : SIP_LQR_LAYOUT_FULL, CORE, STAGED, /*solve_only*/ true,                   \
+    MRHS(N, M, STAGED, SYM), SPLIT(N, M, STAGED, SYM) }

@@ -26,10 +26,13 @@ namespace sipamd {
 typedef hipError_t (*launch_fs_t)(long batch, int T, const void *mats, const void *vecs, void *sol, void *gains,
                                   int32_t *status, void *ws, hipStream_t stream, int mode, void *gfac);
 
-// LQR::solve for `ncols` right-hand sides in one sweep (chain_mrhs.hpp); columns `col_stride` scalars apart
-typedef hipError_t (*launch_mrhs_t)(long batch, int T, const void *mats, const void *vecs_cols, void *sol_cols,
-                                    const void *gains, const void *ws, const void *gfac, void *cws,
-                                    const int32_t *status, int ncols, long col_stride, hipStream_t stream);
+// A column sweep: LQR::solve for `ncols` right-hand sides `col_stride` scalars apart against a kept factor state.
+// chain_mrhs.hpp (ncols <= kMrhsColumns; reads gains and ws only) and the solve sweep of the n = 32 matrix-core kernels
+// (mt16_launch.hpp; ncols <= kMt16SolveColumns).  cws != nullptr: g and k of the columns go through the column
+// workspace; cws == nullptr (the n = 32 sweep, ncols == 1): through the spill and the k part of `gains`.
+typedef hipError_t (*launch_cols_t)(long batch, int T, const void *mats, const void *vecs_cols, void *sol_cols,
+                                    void *gains, void *ws, const void *gfac, void *cws, const int32_t *status,
+                                    int ncols, long col_stride, hipStream_t stream);
 constexpr int kMrhsColumns = 8; // columns one multi-rhs launch carries
 
 // The split form of the fused sweep (sip_lqr_factor_solve_split): mats carries [Q | delta | M | R] per
@@ -39,28 +42,32 @@ typedef hipError_t (*launch_split_t)(long batch, int T, const void *mats, const 
                                      void *ws, hipStream_t stream);
 
 // The separate sweeps of the n = 32 matrix-core kernels (sip_lqr_plan_set_separate_sweeps; mt16_launch.hpp).
-// Factor sweep: W per node to `ws`, K to `gains`, -G^-1 per edge to `gfac` (M * M + M scalars per edge), the statuses.
+// Factor sweep: W per node to `ws`, K to `gains`, -G^-1 per edge to `gfac` (M * M + M scalars per edge), the statuses;
+// the solve sweep is a launch_cols_t.
 typedef hipError_t (*launch_factor_sweep_t)(long batch, int T, const void *mats, void *gains, int32_t *status, void *ws,
                                             void *gfac, hipStream_t stream);
-// Solve sweep for 1 <= ncols <= 16 right-hand sides `col_stride` scalars apart.  cws != nullptr: g and k of the columns
-// go through the column workspace; cws == nullptr (ncols == 1): through the spill and the k part of `gains`.
-typedef hipError_t (*launch_solve_sweep_t)(long batch, int T, const void *mats, const void *vecs_cols, void *sol_cols,
-                                           void *gains, void *ws, const void *gfac, void *cws, const int32_t *status,
-                                           int ncols, long col_stride, hipStream_t stream);
 
+// The first six members every family has; an entry macro names, after them, only what its family adds.
 struct KernelEntry {
   int dtype, n, m;
   const char *name;
   int ws_slot; // scalars of workspace per node
   launch_fs_t launch_fs;
-  launch_mrhs_t launch_mrhs;   // nullptr: this shape solves several right-hand sides column by column
-  int layout;                  // SIP_LQR_LAYOUT_* of mats the kernel reads (0: the full squares)
-  bool core;                   // a slice entry that SIP_LQR_EXTRA=0 leaves visible
-  launch_split_t launch_split; // nullptr: no split form of this kernel
-  // both nullptr: the kernel has no separate factor / solve sweeps to opt into
+  // the fp64 fused kernels (QW16_ENTRY)
+  int layout = SIP_LQR_LAYOUT_FULL;      // SIP_LQR_LAYOUT_* of mats the kernel reads
+  bool core = false;                     // a slice entry that SIP_LQR_EXTRA=0 leaves visible
+  bool staged = false;                   // operands by LDS-DMA: find_embedding_kernel prefers these hosts
+  bool solve_only = false;               // launch_fs honours mode 2 (else a split solve re-runs the full sweep)
+  launch_cols_t launch_mrhs = nullptr;   // nullptr: this shape solves several right-hand sides column by column
+  launch_split_t launch_split = nullptr; // nullptr: no split form of this kernel
+  // the n = 32 matrix-core kernels (MT16_ENTRY); both nullptr: no separate factor / solve sweeps to opt into
   launch_factor_sweep_t launch_factor_sweep = nullptr;
-  launch_solve_sweep_t launch_solve_sweep = nullptr;
+  launch_cols_t launch_solve_sweep = nullptr;
 };
+constexpr KernelEntry with_separate_sweeps(KernelEntry k, launch_factor_sweep_t factor, launch_cols_t solve) {
+  k.launch_factor_sweep = factor, k.launch_solve_sweep = solve;
+  return k;
+}
 
 // slice s of qw16_kernels.hip defines qw16_slice_<s>: its share of the manifest's entries
 #define SIP_QW16_DECLARE_SLICE(S) const KernelEntry *qw16_slice_##S(int *count);

@@ -218,12 +218,7 @@ void first_order_commit(sip_kkt_plan *p, const int th, std::vector<long> (&off)[
   p->fo_uniform = same;
 }
 
-int report(hipError_t e, const char *what) {
-  if (e == hipSuccess)
-    return SIP_LQR_OK;
-  std::fprintf(stderr, "%s: %s\n", what, hipGetErrorString(e));
-  return SIP_LQR_ERR_HIP;
-}
+using sipamd::report;
 
 struct Regions {
   double *in0, *in1, *out, *gain, *inv;

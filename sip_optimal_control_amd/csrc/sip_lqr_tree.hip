@@ -265,11 +265,7 @@ int sip_lqr_tree_factor(const sip_lqr_tree_plan *plan, const double *d_input,
   if ((d_input == nullptr && plan->g.in0_len > 0) || d_work == nullptr)
     return SIP_LQR_ERR_INVALID_ARGUMENT;
   const hipError_t e = plan->g.launch_factor<double>((long)plan->batch, d_input, d_work, d_work, d_status, s);
-  if (e != hipSuccess) {
-    std::fprintf(stderr, "sip_lqr_tree_factor: %s\n", hipGetErrorString(e));
-    return SIP_LQR_ERR_HIP;
-  }
-  return SIP_LQR_OK;
+  return sipamd::report(e, "sip_lqr_tree_factor");
 }
 
 int sip_lqr_tree_solve(const sip_lqr_tree_plan *plan, const double *d_input,
@@ -285,11 +281,7 @@ int sip_lqr_tree_solve(const sip_lqr_tree_plan *plan, const double *d_input,
     return SIP_LQR_ERR_HIP;
   const hipError_t e = plan->g.launch_solve<double>((long)plan->batch, d_input, d_input, d_work, d_work,
                                                     d_output, d_status, (hipStream_t)stream);
-  if (e != hipSuccess) {
-    std::fprintf(stderr, "sip_lqr_tree_solve: %s\n", hipGetErrorString(e));
-    return SIP_LQR_ERR_HIP;
-  }
-  return SIP_LQR_OK;
+  return sipamd::report(e, "sip_lqr_tree_solve");
 }
 
 
@@ -344,11 +336,7 @@ int sip_lqr_tree_solve_multi(const sip_lqr_tree_plan *plan, const double *d_inpu
       e = hipGetLastError();
     }
   }
-  if (e != hipSuccess) {
-    std::fprintf(stderr, "sip_lqr_tree_solve_multi: %s\n", hipGetErrorString(e));
-    return SIP_LQR_ERR_HIP;
-  }
-  return SIP_LQR_OK;
+  return sipamd::report(e, "sip_lqr_tree_solve_multi");
 }
 
 const char *sip_lqr_tree_multi_kernel_name(const sip_lqr_tree_plan *plan) {
@@ -388,11 +376,7 @@ int tree_factor_solve_impl(const sip_lqr_tree_plan *plan, const double *d_input,
   const auto launch = workspace ? plan->fused->launch_export : plan->fused->launch;
   const hipError_t e = launch(plan->sched, d_input, d_output, d_work, (double *)w, (double *)(w + plan->at_spill),
                               d_status, (long)plan->batch, s);
-  if (e != hipSuccess) {
-    std::fprintf(stderr, "sip_lqr_tree_factor_solve: %s\n", hipGetErrorString(e));
-    return SIP_LQR_ERR_HIP;
-  }
-  return SIP_LQR_OK;
+  return sipamd::report(e, "sip_lqr_tree_factor_solve");
 }
 } // namespace
 
@@ -420,11 +404,7 @@ int sip_lqr_tree_factor_fused(const sip_lqr_tree_plan *plan, const double *d_inp
   char *w = (char *)d_scratch;
   const hipError_t e = plan->fused->launch_factor(plan->sched, d_input, d_work, (double *)w, (double *)(w + plan->at_spill),
                                                   d_status, (long)plan->batch, (hipStream_t)stream);
-  if (e != hipSuccess) {
-    std::fprintf(stderr, "sip_lqr_tree_factor_fused: %s\n", hipGetErrorString(e));
-    return SIP_LQR_ERR_HIP;
-  }
-  return SIP_LQR_OK;
+  return sipamd::report(e, "sip_lqr_tree_factor_fused");
 }
 
 int sip_lqr_tree_solve_fused(const sip_lqr_tree_plan *plan, const double *d_input, double *d_work, double *d_output,
@@ -443,11 +423,7 @@ int sip_lqr_tree_solve_fused(const sip_lqr_tree_plan *plan, const double *d_inpu
     return SIP_LQR_ERR_HIP;
   const hipError_t e = plan->fused->launch_solve(plan->sched, d_input, d_work, d_output, d_status, (long)plan->batch,
                                                  (hipStream_t)stream);
-  if (e != hipSuccess) {
-    std::fprintf(stderr, "sip_lqr_tree_solve_fused: %s\n", hipGetErrorString(e));
-    return SIP_LQR_ERR_HIP;
-  }
-  return SIP_LQR_OK;
+  return sipamd::report(e, "sip_lqr_tree_solve_fused");
 }
 
 const char *sip_lqr_tree_split_kernel_name(const sip_lqr_tree_plan *plan) {

@@ -11,6 +11,9 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
+
+#include "../../include/sip_lqr_amd.h"
 
 namespace sipamd {
 
@@ -36,6 +39,14 @@ struct DeviceGuard {
   DeviceGuard(const DeviceGuard &) = delete;
   DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
+
+// The return code of an entry point that ends with HIP status `e`; a failure is named on stderr.
+inline int report(hipError_t e, const char *what) {
+  if (e == hipSuccess)
+    return SIP_LQR_OK;
+  std::fprintf(stderr, "%s: %s\n", what, hipGetErrorString(e));
+  return SIP_LQR_ERR_HIP;
+}
 
 // 4-byte words (every region filled or copied here is int32 / float / double data, 4-byte aligned)
 static __global__ void __launch_bounds__(256) fill_zero_kernel(uint32_t *__restrict__ dst, long words) {
