@@ -138,7 +138,18 @@ void sip_lqr_plan_destroy(sip_lqr_plan *plan);
  * sweep does so in fp64 only: K from sip_lqr_factor on an opt-in plan agrees with K from sip_lqr_factor_solve on the
  * same plan to rounding (in fp32 it is the more accurate one on badly scaled problems), NOT bitwise.  sip_lqr_solve and
  * sip_lqr_solve_multi leave `sol` of a problem whose factorization failed untouched, on exact and embedded shapes.
- * Call once, right after plan creation, before any size is read.  Other plans: SIP_LQR_OK, nothing changes.
+ * The same call on a plan on which sip_lqr_plan_set_fused_f32 took effect BEFORE it (every row of that kernel; not with
+ * SIP_LQR_SPLIT=general): sip_lqr_factor runs chain_factor_qf32, the backward matrix sweep alone, and keeps S = F^-1 per
+ * node, K, the LDL factor of G per edge and the statuses; sip_lqr_solve runs chain_solve_cols_qf32 on one column against
+ * that state (it reads A, B and delta of `mats`, not the cost) and leaves K | k in `gains`; sip_lqr_solve_multi carries
+ * up to 8 columns per sweep.  sip_lqr_kernel_name gains the suffix " + chain_factor_qf32 + chain_solve_qf32";
+ * sip_lqr_workspace_bytes does not change; sip_lqr_solve_multi_workspace_bytes(plan, c) becomes
+ * batch * 4 * (T + 1) * min(c, 8) * (2 n + m) (g | h | k per node and column).  sip_lqr_factor_solve is unaffected,
+ * bitwise.  sip_lqr_solve and sip_lqr_solve_multi leave `sol` of a problem whose factorization failed untouched.  In
+ * the other call order (this call first, then sip_lqr_plan_set_fused_f32) nothing changes here and the plan is the
+ * fused-fp32-only plan.
+ * Call once, right after plan creation (after sip_lqr_plan_set_fused_f32 where both are wanted), before any size is
+ * read.  Other plans: SIP_LQR_OK, nothing changes.
  * on = 0: nothing changes.  SIP_LQR_ERR_INVALID_ARGUMENT: NULL plan, or a second call with on = 1. */
 int sip_lqr_plan_set_separate_sweeps(sip_lqr_plan *plan, int on);
 int sip_lqr_has_separate_sweeps(const sip_lqr_plan *plan); /* 1 after a successful opt-in that took effect */
@@ -151,7 +162,9 @@ int sip_lqr_has_separate_sweeps(const sip_lqr_plan *plan); /* 1 after a successf
  * becomes the larger of the fused and the general layout (it does not shrink); the per-problem lengths are unchanged.
  * sip_lqr_factor, sip_lqr_solve and sip_lqr_solve_multi re-run the full sweep (factor on a zero right-hand side,
  * solve_multi column by column, sip_lqr_solve_multi_workspace_bytes stays 0), unless SIP_LQR_SPLIT=general keeps them
- * on the general engine; sip_lqr_solve then computes bitwise what sip_lqr_factor_solve computes.  Statuses are exact;
+ * on the general engine; sip_lqr_solve then computes bitwise what sip_lqr_factor_solve computes.
+ * sip_lqr_plan_set_separate_sweeps AFTER this call gives the three split calls sweeps of their own (one factorisation
+ * for a factor followed by any number of solves; see there).  Statuses are exact;
  * sol and gains of a problem whose status != SUCCESS are unspecified, as for every fused kernel.
  * Call once, right after plan creation, before any size is read.  fp64 plans, fp32 plans whose shape has no row
  * (n = 16 and n = 32 among them), plans created under SIP_LQR_VARIANT=general, and on = 0: SIP_LQR_OK, nothing

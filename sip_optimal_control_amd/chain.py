@@ -38,12 +38,13 @@ class BatchedChainLQR:
 
     def __init__(self, n, m, T, batch, dtype=torch.float64, device="cuda:0", symmetric=False, separate_sweeps=False,
                  fused_f32=False):
-        """separate_sweeps=True: on plans of the n = 32 matrix-core kernel (16 < n <= 32, m <= 8), factor() runs the
-        matrix sweep alone, solve() a vector-only sweep against it and solve_multi() up to 16 columns per sweep
-        (sip_lqr_plan_set_separate_sweeps; a no-op on other plans, see `has_separate_sweeps`).
-        fused_f32=True: an fp32 plan whose (n, m) has a fused fp32 kernel (n <= 15, m <= 8: the benchmark grid
+        """fused_f32=True: an fp32 plan whose (n, m) has a fused fp32 kernel (n <= 15, m <= 8: the benchmark grid
         n in {4, 6, 8, 12} x m in {1, 2, 3, 4} and a few more) runs on it instead of the general engine
         (sip_lqr_plan_set_fused_f32; a no-op on other plans, see `has_fused_f32`).
+        separate_sweeps=True: on plans of the n = 32 matrix-core kernel (16 < n <= 32, m <= 8) and on plans on which
+        fused_f32 took effect (it is applied first), factor() runs the matrix sweep alone, solve() a vector-only
+        sweep against it and solve_multi() up to 16 (n = 32) or 8 (fused fp32) columns per sweep
+        (sip_lqr_plan_set_separate_sweeps; a no-op on other plans, see `has_separate_sweeps`).
         symmetric=True: `mats` in SIP_LQR_LAYOUT_SYMMETRIC (Q, R as packed lower triangles; ChainShape.pack_index
         converts a full-layout batch); raises for shapes without a symmetric-packed kernel."""
         self._lib = load_library()
@@ -56,10 +57,10 @@ class BatchedChainLQR:
                                                     1 if symmetric else 0, ctypes.byref(handle)),
                f"sip_lqr_plan_create_layout(n={n}, m={m}, T={T}, {dtype}, symmetric={bool(symmetric)})")
         self._plan = handle
-        if separate_sweeps:  # before any size is read
-            _check(self._lib.sip_lqr_plan_set_separate_sweeps(handle, 1), "sip_lqr_plan_set_separate_sweeps")
-        if fused_f32:  # likewise
+        if fused_f32:  # before any size is read
             _check(self._lib.sip_lqr_plan_set_fused_f32(handle, 1), "sip_lqr_plan_set_fused_f32")
+        if separate_sweeps:  # likewise; after fused_f32: the fused fp32 rows have separate sweeps to opt into
+            _check(self._lib.sip_lqr_plan_set_separate_sweeps(handle, 1), "sip_lqr_plan_set_separate_sweeps")
         esize = torch.empty((), dtype=dtype).element_size()
         assert self._lib.sip_lqr_mats_len(handle) == self.shape.mats_len
         assert self._lib.sip_lqr_vecs_len(handle) == self.shape.vecs_len
@@ -197,8 +198,8 @@ class BatchedChainLQR:
     def solve_multi(self, mats, vecs_cols, gains, sol_cols=None, stream=None):
         """LQR::solve() for several right-hand sides against the last factor() (the multi-rhs block of
         solve_stagewise_kkt_matrix, helpers.cpp:521-665): vecs_cols / sol_cols are [num_rhs, batch,
-        vecs_len].  One sweep per 8 columns where the shape has the multi-rhs kernel (per 16 on the n = 32
-        plans with separate_sweeps)."""
+        vecs_len].  One sweep per 8 columns where the shape has the multi-rhs kernel or the plan runs the fused fp32
+        kernel with separate_sweeps (per 16 on the n = 32 plans with separate_sweeps); column by column otherwise."""
         s = self.shape
         num_rhs = vecs_cols.shape[0]
         if sol_cols is None:

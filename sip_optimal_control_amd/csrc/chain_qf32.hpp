@@ -22,8 +22,8 @@
 // more rounding in a recursion of fp32 roundings.  Only compiler-scheduled instructions consume them, so the TRANS
 // forwarding hazard is the compiler's to pad.
 //
-// Not here: LDS-DMA staging, the split (A | B in place) form, the symmetric-packed layout, a
-// vector-only solve mode, several right-hand sides per sweep, n = 16.
+// The matrix sweep alone, a vector-only solve and several right-hand sides per sweep: chain_qf32_sweeps.hpp.
+// Not here: LDS-DMA staging, the split (A | B in place) form, the symmetric-packed layout, n = 16.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -64,7 +64,11 @@ __device__ __forceinline__ float bcast(float x) {
 // (lanes c < S).  On exit lane j holds Lt(i,j) = L(i,j) * L(j,j) in A[i], i >= j (so A[j] of lane j is the pivot
 // d_j = L(j,j)^2 of the Cholesky factor) and dinv[k] = 1 / d_k replicated in every lane.  Returns true on failure
 // (some pivot <= 0; a NaN pivot passes, as it passes an `x <= 0` test).
-template <int S>
+// WAIT0: the first rank-1 update carries its own wait states.  It reads columns of A that the caller's
+// compiler-scheduled instructions wrote; the compiler may place such a write right before the asm block, whose DPP reads
+// it does not see.  (The later updates follow the s_nop of bcast.)  The fused kernel's schedule keeps the distance
+// (its listing is checked) and stays as it was compiled: false.
+template <int S, bool WAIT0 = false>
 __device__ __forceinline__ bool chol_ldl_dpp(float (&A)[S], float (&dinv)[S], const int c) {
   float dmin = __builtin_inff(); // the smallest pivot so far, row-replicated like the pivots
   sfor<0, S>([&](auto kk) {
@@ -77,7 +81,7 @@ __device__ __forceinline__ bool chol_ldl_dpp(float (&A)[S], float (&dinv)[S], co
     dinv[k] = y2;
     const float upd = own * y2; // Lt(j,k) / d_k
     // A(i,j) -= Lt(i,k) Lt(j,k) / d_k, i > k, lanes j > k
-    rank1<S - k - 1, k, true, false>(A + k + 1, A + k + 1, upd);
+    rank1<S - k - 1, k, true, (WAIT0 && k == 0)>(A + k + 1, A + k + 1, upd);
   });
   return dmin <= 0.0f;
 }
@@ -103,8 +107,8 @@ __device__ __forceinline__ void ldl_solve_dpp(const float (&Lt)[S], const float 
 
 // F_factor / W of one node.  V: column c of V (lanes < N).  dl: delta_c one per lane (1 on lanes >= N).  tv:
 // c - delta o v on the vector lane, zeros elsewhere.  X returns S = F^{-1} (lanes < N) and, on the vector lane,
-// S D^{-1/2} tv; W = D^{-1/2} (I - S) D^{-1/2}.  Returns pivot failure.
-template <int N>
+// S D^{-1/2} tv; W = D^{-1/2} (I - S) D^{-1/2}.  Returns pivot failure.  WAIT0: see chol_ldl_dpp.
+template <int N, bool WAIT0 = false>
 __device__ __forceinline__ bool node_factor(const float (&V)[N], const float dl, const int c, const float (&E)[N],
                                             const float (&tv)[N], float (&W)[N], float (&X)[N]) {
   const float sdi = __builtin_amdgcn_rsqf(dl); // 1 / sqrt(delta)
@@ -116,7 +120,7 @@ __device__ __forceinline__ bool node_factor(const float (&V)[N], const float dl,
     constexpr int r = decltype(ii)::value;
     A[r] = __builtin_fmaf(S[r], V[r], E[r]); // I + D^1/2 V D^1/2
   });
-  const bool fail = chol_ldl_dpp<N>(A, rinv, c);
+  const bool fail = chol_ldl_dpp<N, WAIT0>(A, rinv, c);
   sfor<0, N>([&](auto ii) { X[decltype(ii)::value] = E[decltype(ii)::value]; });
   spreadv<N, false>(X, sdi, tv); // vector lane: D^{-1/2} (c - delta o v)
   ldl_solve_dpp<N>(A, rinv, X);  // F^{-1} [I | .]

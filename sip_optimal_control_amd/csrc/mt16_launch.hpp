@@ -19,6 +19,7 @@ constexpr int kMt16SpillPerNode = 3 * 256 + 32; // Layout::WSN: three tiles of t
 // qw16_table.hpp, instantiated in chain_mt16_solve.hip (chain_factor_mt16, chain_solve_mt16) ----
 constexpr int kMt16SolveColumns = 16; // the columns of a 16 x 16 tile
 constexpr long mt16_col_workspace_scalars(int T, int m, int ncols) { return (long)(T + 1) * ncols * (32 + m); }
+constexpr char kSeparateSuffix[] = " + chain_factor_mt16 + chain_solve_mt16"; // what the opt-in appends to the name
 
 template <typename S, int M>
 hipError_t launch_mt16_factor(long batch, int T, const void *mats, void *gains, int32_t *status, void *ws, void *gfac,
@@ -33,4 +34,5 @@ hipError_t launch_mt16_solve(long batch, int T, const void *mats, const void *ve
 #define MT16_ENTRY(DT, S, TAG, M)                                                                            \
   sipamd::with_separate_sweeps({DT, 32, M, "chain_factor_solve_mt16<32," #M ",mfma16x16x4>/" TAG,            \
                                 sipamd::kMt16SpillPerNode, &sipamd::launch_mt16<S, M>},                      \
-                               &sipamd::launch_mt16_factor<S, M>, &sipamd::launch_mt16_solve<S, M>)
+                               {&sipamd::launch_mt16_factor<S, M>, &sipamd::launch_mt16_solve<S, M>,         \
+                                sipamd::kSeparateSuffix, sipamd::kMt16SolveColumns, 32 + M})

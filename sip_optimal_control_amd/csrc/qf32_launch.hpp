@@ -1,6 +1,7 @@
-// qf32_launch.hpp -- the rows, the layout and the launcher of the fused fp32 chain kernel (chain_qf32.hpp),
-// instantiated in chain_qf32.hip (a translation unit of its own).  No kernel source in here: the host code that looks
-// kernels up (sip_lqr_amd.hip) includes this header alone.
+// qf32_launch.hpp -- the rows, the layout and the launchers of the fused fp32 chain kernel (chain_qf32.hpp, instantiated
+// in chain_qf32.hip) and of its separate sweeps (chain_qf32_sweeps.hpp, instantiated in chain_qf32_sweeps.hip), each a
+// translation unit of its own.  No kernel source in here: the host code that looks kernels up (sip_lqr_amd.hip)
+// includes this header alone.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,15 +35,32 @@ struct Layout {
 };
 
 // launch_fs_t of qw16_table.hpp; `mode` and `gfac` are ignored: the kernel always runs the full sweep (split
-// factor / solve calls re-run it, see sip_lqr_plan::split_on_fused).
+// factor / solve calls re-run it, see sip_lqr_plan::split_on_fused, unless the plan opted into the sweeps below).
 template <int N, int M>
 hipError_t launch_qf32(long batch, int T, const void *mats, const void *vecs, void *sol, void *gains, int32_t *status,
                        void *ws, hipStream_t stream, int mode, void *gfac);
+
+// ---- the separate sweeps (sip_lqr_plan_set_separate_sweeps after sip_lqr_plan_set_fused_f32): launch_factor_sweep_t /
+// launch_cols_t of qw16_table.hpp (chain_factor_qf32, chain_solve_cols_qf32) ----
+constexpr int kQf32SolveColumns = 8; // columns one solve sweep carries
+// cws[node][column][g (n) | h (n) | k (m)] of one problem
+constexpr long qf32_col_workspace_scalars(int T, int n, int m, int ncols) { return (long)(T + 1) * ncols * (2 * n + m); }
+constexpr char kQf32SeparateSuffix[] = " + chain_factor_qf32 + chain_solve_qf32";
+
+template <int N, int M>
+hipError_t launch_qf32_factor(long batch, int T, const void *mats, void *gains, int32_t *status, void *ws, void *gfac,
+                              hipStream_t stream);
+template <int N, int M>
+hipError_t launch_qf32_solve(long batch, int T, const void *mats, const void *vecs_cols, void *sol_cols, void *gains,
+                             void *ws, const void *gfac, void *cws, const int32_t *status, int ncols, long col_stride,
+                             hipStream_t stream);
 
 } // namespace qf32
 } // namespace sipamd
 
 // One row of the opt-in table (sip_lqr_plan_set_fused_f32): never part of find_kernel's search.
 #define QF32_ENTRY(N, M)                                                                                     \
-  {SIP_LQR_F32, N, M, "chain_factor_solve_qf32<" #N "," #M ",direct>/f32", sipamd::qf32::Layout<N, M>::WSN,   \
-   &sipamd::qf32::launch_qf32<N, M>},
+  sipamd::with_separate_sweeps({SIP_LQR_F32, N, M, "chain_factor_solve_qf32<" #N "," #M ",direct>/f32",      \
+                                sipamd::qf32::Layout<N, M>::WSN, &sipamd::qf32::launch_qf32<N, M>},          \
+                               {&sipamd::qf32::launch_qf32_factor<N, M>, &sipamd::qf32::launch_qf32_solve<N, M>, \
+                                sipamd::qf32::kQf32SeparateSuffix, sipamd::qf32::kQf32SolveColumns, 2 * N + M}),

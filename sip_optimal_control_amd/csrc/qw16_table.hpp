@@ -27,9 +27,10 @@ typedef hipError_t (*launch_fs_t)(long batch, int T, const void *mats, const voi
                                   int32_t *status, void *ws, hipStream_t stream, int mode, void *gfac);
 
 // A column sweep: LQR::solve for `ncols` right-hand sides `col_stride` scalars apart against a kept factor state.
-// chain_mrhs.hpp (ncols <= kMrhsColumns; reads gains and ws only) and the solve sweep of the n = 32 matrix-core kernels
-// (mt16_launch.hpp; ncols <= kMt16SolveColumns).  cws != nullptr: g and k of the columns go through the column
-// workspace; cws == nullptr (the n = 32 sweep, ncols == 1): through the spill and the k part of `gains`.
+// chain_mrhs.hpp (ncols <= kMrhsColumns; reads gains and ws only) and the solve sweeps of the n = 32 matrix-core kernels
+// (mt16_launch.hpp; ncols <= kMt16SolveColumns) and of the fused fp32 kernels (qf32_launch.hpp; ncols <=
+// kQf32SolveColumns).  cws != nullptr: the per-column state of the rollout goes through the column workspace;
+// cws == nullptr (a solve sweep, ncols == 1): through the spill and the k part of `gains`.
 typedef hipError_t (*launch_cols_t)(long batch, int T, const void *mats, const void *vecs_cols, void *sol_cols,
                                     void *gains, void *ws, const void *gfac, void *cws, const int32_t *status,
                                     int ncols, long col_stride, hipStream_t stream);
@@ -60,12 +61,24 @@ struct KernelEntry {
   bool solve_only = false;               // launch_fs honours mode 2 (else a split solve re-runs the full sweep)
   launch_cols_t launch_mrhs = nullptr;   // nullptr: this shape solves several right-hand sides column by column
   launch_split_t launch_split = nullptr; // nullptr: no split form of this kernel
-  // the n = 32 matrix-core kernels (MT16_ENTRY); both nullptr: no separate factor / solve sweeps to opt into
+  // the n = 32 matrix-core kernels (MT16_ENTRY) and the fused fp32 kernels (QF32_ENTRY); both nullptr: no separate
+  // factor / solve sweeps to opt into
   launch_factor_sweep_t launch_factor_sweep = nullptr;
   launch_cols_t launch_solve_sweep = nullptr;
+  const char *separate_suffix = "";      // what the opt-in appends to the plan's kernel name
+  int sweep_columns = 0;                 // columns one launch of launch_solve_sweep carries
+  int sweep_col_scalars = 0;             // scalars of column workspace per node and column
 };
-constexpr KernelEntry with_separate_sweeps(KernelEntry k, launch_factor_sweep_t factor, launch_cols_t solve) {
-  k.launch_factor_sweep = factor, k.launch_solve_sweep = solve;
+// The separate sweeps of a row, and how its solve sweep carries columns.
+struct SeparateSweeps {
+  launch_factor_sweep_t factor;
+  launch_cols_t solve;
+  const char *suffix;
+  int columns, col_scalars;
+};
+constexpr KernelEntry with_separate_sweeps(KernelEntry k, SeparateSweeps s) {
+  k.launch_factor_sweep = s.factor, k.launch_solve_sweep = s.solve;
+  k.separate_suffix = s.suffix, k.sweep_columns = s.columns, k.sweep_col_scalars = s.col_scalars;
   return k;
 }
 

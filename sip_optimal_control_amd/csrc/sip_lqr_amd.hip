@@ -60,7 +60,7 @@ struct sip_lqr_plan {
   bool padded = false;
   sipamd::embed::PadDims dims{};
   // sip_lqr_plan_set_separate_sweeps on a plan whose kernel row has them: factor and solve as sweeps of their own
-  // (chain_factor_mt16, chain_solve_mt16)
+  // (chain_factor_mt16, chain_solve_mt16; chain_factor_qf32, chain_solve_cols_qf32 on a plan with fused_f32)
   bool separate = false;
   // sip_lqr_plan_set_fused_f32 on an fp32 plan of the general engine whose shape has a row in kQf32Rows: the plan
   // runs on chain_factor_solve_qf32.  forced_general: SIP_LQR_VARIANT=general at creation, which the opt-in respects
@@ -111,7 +111,6 @@ const KernelEntry kKernels[] = {
     MT16_ENTRY(SIP_LQR_F64, double, "f64", 8), MT16_ENTRY(SIP_LQR_F64, double, "f64", 4),
     MF32(8),
 };
-const char kSeparateSuffix[] = " + chain_factor_mt16 + chain_solve_mt16";
 
 // fp32, n <= 15: four problems per wavefront on v_fmac_f32_dpp (chain_qf32.hpp).  A table of its own that find_kernel
 // never searches: a plan gets one of these rows through sip_lqr_plan_set_fused_f32 alone.
@@ -253,9 +252,11 @@ struct ColumnSweep {
 ColumnSweep column_sweep(const sip_lqr_plan *p, int num_rhs) {
   if (p->kernel == nullptr || p->padded || !p->split_on_fused)
     return {};
-  if (p->separate) // the solve sweep of the n = 32 kernel: g | k per node and column
-    return {p->kernel->launch_solve_sweep, sipamd::kMt16SolveColumns,
-            sipamd::mt16_col_workspace_scalars(p->T, p->m, std::min(num_rhs, sipamd::kMt16SolveColumns))};
+  if (p->separate) { // the solve sweep of the row: what it keeps per node and column is the row's to say
+    const KernelEntry &k = *p->kernel;
+    return {k.launch_solve_sweep, k.sweep_columns,
+            (long)(p->T + 1) * std::min(num_rhs, k.sweep_columns) * k.sweep_col_scalars};
+  }
   if (p->kernel->launch_mrhs != nullptr) // chain_mrhs.hpp: g | h | k per node and column
     return {p->kernel->launch_mrhs, sipamd::kMrhsColumns,
             (long)(p->T + 1) * std::min(num_rhs, sipamd::kMrhsColumns) * (2 * p->n + p->m)};
@@ -402,9 +403,9 @@ int sip_lqr_plan_set_separate_sweeps(sip_lqr_plan *plan, int on) {
       plan->kernel->launch_solve_sweep == nullptr)
     return SIP_LQR_OK; // the plan's kernel has no such sweeps (or its split calls run on the general engine)
   plan->separate = true;
-  // the workspace stays what it was: the spill, the scratch of the split calls and the gfac region (-G^-1 per edge)
-  // are those workspace_layout already reserves
-  std::string name = std::string(plan->kernel_name) + kSeparateSuffix;
+  // the workspace stays what it was: the spill, the scratch of the split calls and the gfac region (M * M + M scalars
+  // per edge) are those workspace_layout already reserves
+  std::string name = std::string(plan->kernel_name) + plan->kernel->separate_suffix;
   plan->name_storage.swap(name);
   plan->kernel_name = plan->name_storage.c_str();
   return SIP_LQR_OK;
@@ -425,8 +426,9 @@ int sip_lqr_plan_set_fused_f32(sip_lqr_plan *plan, int on) {
   if (row == nullptr)
     return SIP_LQR_OK; // no fused fp32 kernel of this shape
   plan->fused_f32 = true;
-  // factor and solve re-run the sweep (the row has no solve-only mode), unless the split calls were asked to stay
-  // general; sip_lqr_workspace_bytes is the larger of the two layouts from here on, as for every fused plan
+  // factor and solve re-run the sweep (until sip_lqr_plan_set_separate_sweeps gives them sweeps of their own), unless
+  // the split calls were asked to stay general; sip_lqr_workspace_bytes is the larger of the two layouts from here on,
+  // as for every fused plan
   decide_kernel(plan, row, false, dispatch_env());
   return SIP_LQR_OK;
 }
@@ -700,7 +702,7 @@ int sip_lqr_solve_multi(const sip_lqr_plan *plan, const void *d_mats, const void
                   (char *)d_sol_cols + (size_t)col0 * col_bytes, d_gains, d_workspace, w + plan->ws.gfac,
                   d_col_workspace, (const int32_t *)(w + plan->ws.status), nc, stride, (hipStream_t)stream);
   }
-  return report(e, plan->separate ? "sip_lqr_solve_multi(mt16)" : "sip_lqr_solve_multi");
+  return report(e, plan->separate ? "sip_lqr_solve_multi(separate sweeps)" : "sip_lqr_solve_multi");
 }
 
 const char *sip_lqr_kernel_name(const sip_lqr_plan *plan) {
