@@ -46,6 +46,13 @@ struct FoUniform {
   int x_dim, y_dim, z_dim;    // stagewise (theta excluded)
   long len;                   // doubles per problem
 };
+// The fields of a FoUniform that follow from its dimensions (n, m, p, cn, gn, ce, ge): the lengths of an interior
+// stage's two items.  The lengths of whole arenas (x / y / z_dim, len) are the plan's and travel as they are.
+constexpr FoUniform fo_uniform_derive(FoUniform fu) {
+  fu.node_len = 1 + fu.n + fu.p + fu.cn + fu.gn;
+  fu.edge_len = 1 + 2 * fu.n + fu.m + fu.p + fu.ce + fu.ge;
+  return fu;
+}
 
 // Work items (problem, node) and (problem, edge); item < N is a node.
 __global__ void __launch_bounds__(FO_TPB)
