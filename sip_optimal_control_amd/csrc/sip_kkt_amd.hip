@@ -14,6 +14,7 @@
 
 #include "generic_plan.hpp"
 #include "stream_fill.hpp"
+#include "table_packer.hpp"
 #include "kkt_plan.hpp"
 
 const sipamd::kkt::KktChainKernels *sipamd::kkt::find_kkt_chain_kernels(const int n, const int m) {
@@ -37,30 +38,10 @@ sip_kkt_plan::~sip_kkt_plan() {
 namespace {
 
 using sipamd::report;
+using sipamd::TablePacker;
 using sipamd::kkt::Meta;
 using sipamd::kkt::ptr;
 namespace kkt = sipamd::kkt; // (the LDS descriptions next to the kernels, and what is derived from them: kkt::...)
-
-// Host vectors on their way into one device array: push a vector and name the pointer that is to point at its copy;
-// upload() allocates the array, copies it and sets every such pointer.
-template <class T>
-struct TablePacker {
-  std::vector<T> flat;
-  std::vector<std::pair<const T **, size_t>> wanted;
-  void push(const std::vector<T> &v, const T **dst = nullptr) {
-    if (dst != nullptr)
-      wanted.push_back({dst, flat.size()});
-    flat.insert(flat.end(), v.begin(), v.end());
-  }
-  hipError_t upload(void **d_mem) {
-    hipError_t e = hipMalloc(d_mem, std::max<size_t>(1, flat.size()) * sizeof(T));
-    if (e == hipSuccess)
-      e = hipMemcpy(*d_mem, flat.data(), flat.size() * sizeof(T), hipMemcpyHostToDevice);
-    for (size_t k = 0; k < wanted.size() && e == hipSuccess; ++k)
-      *wanted[k].first = (const T *)*d_mem + wanted[k].second;
-    return e;
-  }
-};
 
 // The preamble of a compute entry point: the plan's device is the current one while this lives, whatever the
 // caller's (which is restored).  rc != SIP_LQR_OK: reported as `what`, to be returned.
@@ -302,6 +283,8 @@ hipError_t upload_tables(sip_kkt_plan *p, const sipamd::GenericPlan &g, const st
   TablePacker<long> longs;
   for (int b = 0; b < kkt::NUM_BLOCKS; ++b)
     longs.push(p->moff[b], &m.mo[b]);
+  // (the twelve LQR tables this Meta has, in its own order: a walk over GenericPlan::kOffsetFields would need a second
+  // table of kkt::Meta members beside it, which is these lines again)
   longs.push(g.oQ, &m.oQ), longs.push(g.od, &m.od), longs.push(g.oq, &m.oq), longs.push(g.oc, &m.oc);
   longs.push(g.ox, &m.ox), longs.push(g.oy, &m.oy), longs.push(g.oA, &m.oA), longs.push(g.oB, &m.oB);
   longs.push(g.oM, &m.oM), longs.push(g.oR, &m.oR), longs.push(g.orr, &m.orr), longs.push(g.ou, &m.ou);

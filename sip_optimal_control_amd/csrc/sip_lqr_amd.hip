@@ -194,17 +194,12 @@ sipamd::ChainLens lens(const sip_lqr_plan *p) { return sipamd::chain_lens(p->n, 
 // Chain topology (Topology::set_chain, lqr.cpp:32-40) for the general engine.
 void init_generic(sip_lqr_plan *p) {
   const int T = p->T, N = T + 1;
-  std::vector<int> sd(N, p->n), cd(T, p->m), pa(T), ch(T), marks(N);
+  std::vector<int> sd(N, p->n), cd(T, p->m), pa(T), ch(T);
   for (int e = 0; e < T; ++e)
     pa[e] = e, ch[e] = e + 1;
   sipamd::GenericPlan &g = p->gen;
   g.set_shape(T, 0, sd.data(), cd.data());
-  g.parents.assign(T, 0), g.children.assign(T, 0);
-  g.child_offsets.assign(N + 1, 0), g.child_edges.assign(T, 0);
-  g.preorder.assign(N, 0), g.postorder.assign(N, 0);
-  (void)sip_lqr_compile_topology(T, 0, pa.data(), ch.data(), g.child_offsets.data(),
-                                 g.child_edges.data(), g.parents.data(), g.children.data(),
-                                 g.preorder.data(), g.postorder.data(), marks.data());
+  (void)g.compile(pa.data(), ch.data());
   g.layout_chain(p->n, p->m, T);
 }
 

@@ -2,6 +2,9 @@
 // own translation unit so that it compiles beside the others.
 #include "tree_qw16_launch.hpp"
 
+#include "tree_qw16.hpp"
+#include "tree_mrhs_qw16.hpp"
+
 namespace sipamd {
 
 namespace {
@@ -48,7 +51,8 @@ long cols_len(const TreeSchedule &ts) {
   return TreeColLayout<N, M>::len(ts);
 }
 #define TREE_CLASS(N, M)                                                                                            \
-  {N, M, "tree_factor_solve_qw16<" #N "," #M ">/f64", &launch<N, M, false>, &launch<N, M, true>,                    \
+  {N, M, TreeLayout<N, M>::GAIN, TreeLayout<N, M>::WS,                                                              \
+   "tree_factor_solve_qw16<" #N "," #M ">/f64", &launch<N, M, false>, &launch<N, M, true>,                          \
    "tree_solve_mrhs_qw16<" #N "," #M ">/f64", &launch_multi<N, M>, &cols_len<N, M>,                                  \
    "tree_factor_qw16<" #N "," #M ">/f64 + tree_solve_qw16<" #N "," #M ">/f64", &launch_factor<N, M>, &launch_solve<N, M>}
 // sorted by cost: the first class that holds the largest node and the largest control wins

@@ -1,16 +1,18 @@
-// tree_qw16_launch.hpp -- table entry of the fused tree kernels (tree_qw16.hip) for the tree C ABI.
+// tree_qw16_launch.hpp -- table entry of the fused tree kernels (tree_qw16.hip) for the tree C ABI.  No kernel is
+// included here: what the host needs to know about a size class, the class reports.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-#include "tree_qw16.hpp"
-#include "tree_mrhs_qw16.hpp"
+#include "tree_schedule.hpp"
 
 namespace sipamd {
 
 struct TreeClass {
   int n, m; // padded state / control dimension of the class
+  // scalars per problem of the fused scratch: padded gains of one edge, spill slot of one node (TreeLayout<n, m>)
+  int gain_scalars, spill_scalars;
   const char *name;
   hipError_t (*launch)(const TreeSchedule &ts, const double *input, double *output, double *work, double *pgains,
                        double *spill, int32_t *status, long batch, hipStream_t s);
