@@ -149,6 +149,17 @@ int sip_kkt_plan_set_tree_fused(sip_kkt_plan *plan, int on);
  * SIP_LQR_OK and changes nothing; on = 0 changes nothing.  SIP_LQR_ERR_INVALID_ARGUMENT: NULL plan, or called after
  * sip_kkt_plan_set_theta or a second time with on = 1. */
 int sip_kkt_plan_set_chain_separate_sweeps(sip_kkt_plan *plan, int on);
+/* Opt-in (on = 1): on a valid uniform-chain plan with 9 <= m <= 16 controls and n <= 32 states, whose Riccati plan
+ * runs on the general engine, sip_lqr_plan_set_wide_controls is applied to that plan: the Riccati part of every entry
+ * point runs the n = 32 matrix-core kernel for 12 or 16 controls (the exact row at n = 32, m in {12, 16}, the
+ * embedding otherwise; not with SIP_LQR_PAD=0 or SIP_LQR_VARIANT=general).  The kernel name follows
+ * sip_lqr_kernel_name, and sip_kkt_work_bytes grows to what that plan needs.  The rules of
+ * sip_kkt_plan_set_tree_fused: call once, right after sip_kkt_plan_create, before sip_kkt_work_bytes is read, before
+ * sip_kkt_plan_set_chain_separate_sweeps (which then gives these rows their separate sweeps) and before
+ * sip_kkt_plan_set_theta; on tree plans and plans it does not apply to it returns SIP_LQR_OK and changes nothing;
+ * on = 0 changes nothing.  SIP_LQR_ERR_INVALID_ARGUMENT: NULL plan, or called after sip_kkt_plan_set_theta or a second
+ * time with on = 1 after a call that took effect. */
+int sip_kkt_plan_set_chain_wide_controls(sip_kkt_plan *plan, int on);
 
 /* Replaces CallbackProvider::factor (helpers.cpp:242-370): checks and inverts
  * the regularization, condenses the constraint Jacobians into Q_mod / M_mod /

@@ -128,7 +128,8 @@ void sip_lqr_plan_destroy(sip_lqr_plan *plan);
 
 /* Opt-in (on = 1), on a plan whose kernel is chain_factor_solve_mt16 (exact (32,4) and (32,8) in fp32 and fp64; in
  * fp64 also the embeddings of 16 < n < 32 / other m <= 8 -- an fp32 plan of such a shape runs on the general engine and
- * the call changes nothing on it; not with SIP_LQR_SPLIT=general): sip_lqr_factor runs the backward
+ * the call changes nothing on it; likewise the rows for 12 and 16 controls and their embeddings on a plan that took
+ * sip_lqr_plan_set_wide_controls BEFORE this call; not with SIP_LQR_SPLIT=general): sip_lqr_factor runs the backward
  * matrix sweep alone and keeps the factor state (W per node, K, -G^-1 per edge, the statuses), sip_lqr_solve a
  * vector-only sweep + rollout against it, sip_lqr_solve_multi up to 16 columns per sweep on the matrix cores.
  * sip_lqr_kernel_name gains the suffix " + chain_factor_mt16 + chain_solve_mt16"; sip_lqr_workspace_bytes does not
@@ -171,6 +172,30 @@ int sip_lqr_has_separate_sweeps(const sip_lqr_plan *plan); /* 1 after a successf
  * changes.  SIP_LQR_ERR_INVALID_ARGUMENT: NULL plan, or a second call with on = 1 after one that took effect. */
 int sip_lqr_plan_set_fused_f32(sip_lqr_plan *plan, int on);
 int sip_lqr_has_fused_f32(const sip_lqr_plan *plan); /* 1 after an opt-in that took effect */
+
+/* Opt-in (on = 1), on a FULL-layout plan that runs on the general engine, was not created under
+ * SIP_LQR_VARIANT=general and has 9 <= m <= 16, n <= 32: the plan takes the n = 32 matrix-core kernel
+ * chain_factor_solve_mt16 in its instantiations for 12 and 16 controls (csrc/chain_mt16_wide.hip; one problem per
+ * wavefront, one fused launch) instead of the general engine's factor and solve launches.
+ *   n = 32, m in {12, 16}, either dtype: the exact row; sip_lqr_kernel_name becomes
+ *     "chain_factor_solve_mt16<32,12,mfma16x16x4>/f64" (or <32,16,...>, or /f32).
+ *   any other fp64 shape in range (n <= 16 included), unless SIP_LQR_PAD=0: embedded in the row with the least M >= m
+ *     by a device-side repack before and after the sweep (extra states and controls decouple exactly); the name
+ *     gains " embedding (n,m)".
+ *   an fp32 shape without an exact row: nothing changes, as for the m <= 8 rows of this kernel.
+ * sip_lqr_workspace_bytes becomes the larger of the fused and the general layout (it does not shrink); the per-problem
+ * lengths are unchanged.  sip_lqr_factor, sip_lqr_solve and sip_lqr_solve_multi re-run the fused sweep (factor on a
+ * zero right-hand side, solve_multi column by column), unless SIP_LQR_SPLIT=general keeps them on the general engine;
+ * sip_lqr_plan_set_separate_sweeps AFTER this call gives them sweeps of their own exactly as on the m <= 8 rows (up to
+ * 16 columns per sweep on the exact rows, the single-column solve per column on embedded shapes; see there).  These
+ * instantiations scale F = I + D^1/2 V D^1/2 to a unit diagonal before they factor it in both precisions.  Statuses are
+ * exact; sol and gains of a problem whose status != SUCCESS are unspecified, as for every fused kernel.  A (n <= 16)
+ * problem embedded in 32 x 32 tiles pays for the whole tile: measure before opting in at small n (README).
+ * Call once, right after plan creation, before any size is read and before sip_lqr_plan_set_separate_sweeps.  Plans
+ * the call does not apply to, and on = 0: SIP_LQR_OK, nothing changes.  SIP_LQR_ERR_INVALID_ARGUMENT: NULL plan, or a
+ * second call with on = 1 after one that took effect. */
+int sip_lqr_plan_set_wide_controls(sip_lqr_plan *plan, int on);
+int sip_lqr_has_wide_controls(const sip_lqr_plan *plan); /* 1 after an opt-in that took effect */
 
 /* Sizes, in bytes, of the whole-batch buffers.  Replace
  * LQR::Workspace::num_bytes / LQR::Output::num_bytes (lqr.hpp:104-106,

@@ -99,6 +99,9 @@ _SIGNATURES = {
     "sip_lqr_has_separate_sweeps": (ctypes.c_int, [_P]),
     "sip_lqr_plan_set_fused_f32": (ctypes.c_int, [_P, ctypes.c_int]),
     "sip_lqr_has_fused_f32": (ctypes.c_int, [_P]),
+    "sip_lqr_plan_set_wide_controls": (ctypes.c_int, [_P, ctypes.c_int]),
+    "sip_lqr_has_wide_controls": (ctypes.c_int, [_P]),
+    "sip_kkt_plan_set_chain_wide_controls": (ctypes.c_int, [_P, ctypes.c_int]),
     "sip_kkt_theta_len": (ctypes.c_size_t, [_P]),
     "sip_kkt_theta_offset": (ctypes.c_size_t, [_P, ctypes.c_int, ctypes.c_int]),
     "sip_kkt_theta_work_bytes": (ctypes.c_size_t, [_P]),

@@ -37,8 +37,12 @@ class BatchedChainLQR:
     """`batch` independent chain problems of horizon T, state dim n, control dim m."""
 
     def __init__(self, n, m, T, batch, dtype=torch.float64, device="cuda:0", symmetric=False, separate_sweeps=False,
-                 fused_f32=False):
-        """fused_f32=True: an fp32 plan whose (n, m) has a fused fp32 kernel (n <= 15, m <= 8: the benchmark grid
+                 fused_f32=False, wide_controls=False):
+        """wide_controls=True: a plan of the general engine with 9 <= m <= 16 controls and n <= 32 runs on the n = 32
+        matrix-core kernel for 12 or 16 controls: n = 32 with m in {12, 16} on the exact kernel in either dtype, every
+        other fp64 shape embedded in the one with the least M >= m (sip_lqr_plan_set_wide_controls; a no-op on other
+        plans, see `has_wide_controls`).  Applied before separate_sweeps, which these rows take like the m <= 8 ones.
+        fused_f32=True: an fp32 plan whose (n, m) has a fused fp32 kernel (n <= 15, m <= 8: the benchmark grid
         n in {4, 6, 8, 12} x m in {1, 2, 3, 4} and a few more) runs on it instead of the general engine
         (sip_lqr_plan_set_fused_f32; a no-op on other plans, see `has_fused_f32`).
         separate_sweeps=True: on plans of the n = 32 matrix-core kernel (16 < n <= 32, m <= 8) and on plans on which
@@ -59,7 +63,9 @@ class BatchedChainLQR:
         self._plan = handle
         if fused_f32:  # before any size is read
             _check(self._lib.sip_lqr_plan_set_fused_f32(handle, 1), "sip_lqr_plan_set_fused_f32")
-        if separate_sweeps:  # likewise; after fused_f32: the fused fp32 rows have separate sweeps to opt into
+        if wide_controls:  # likewise
+            _check(self._lib.sip_lqr_plan_set_wide_controls(handle, 1), "sip_lqr_plan_set_wide_controls")
+        if separate_sweeps:  # likewise; after fused_f32 and wide_controls: their rows have separate sweeps to opt into
             _check(self._lib.sip_lqr_plan_set_separate_sweeps(handle, 1), "sip_lqr_plan_set_separate_sweeps")
         esize = torch.empty((), dtype=dtype).element_size()
         assert self._lib.sip_lqr_mats_len(handle) == self.shape.mats_len
@@ -82,6 +88,11 @@ class BatchedChainLQR:
     def has_fused_f32(self):
         """True when the fused_f32 opt-in took effect on this plan."""
         return bool(self._lib.sip_lqr_has_fused_f32(self._plan))
+
+    @property
+    def has_wide_controls(self):
+        """True when the wide_controls opt-in took effect on this plan."""
+        return bool(self._lib.sip_lqr_has_wide_controls(self._plan))
 
     def empty_sol(self):
         return torch.empty(self.batch, self.shape.vecs_len, dtype=self.dtype, device=self.device)

@@ -4,18 +4,6 @@
 
 namespace sipamd {
 
-template <typename S, int M>
-hipError_t launch_mt16(long batch, int T, const void *mats, const void *vecs, void *sol, void *gains,
-                       int32_t *status, void *ws, hipStream_t stream, int /*mode: always the full sweep*/,
-                       void * /*gfac*/) {
-  // 16-byte loads of the stage blocks (fp32, even m) and of the W dump: bases must be 16-byte aligned
-  if (((uintptr_t)mats | (uintptr_t)ws) & 15)
-    return hipErrorInvalidValue;
-  hipLaunchKernelGGL((mt16::chain_factor_solve_mt16<S, M>), dim3((unsigned)batch), dim3(64), 0, stream,
-                     (const S *)mats, (const S *)vecs, (S *)sol, (S *)gains, (S *)ws, (int *)status, batch, T);
-  return hipGetLastError();
-}
-
 static_assert(mt16::Layout<float, 8>::WSN == kMt16SpillPerNode && mt16::Layout<double, 4>::WSN == kMt16SpillPerNode,
               "the dispatch table sizes the workspace by kMt16SpillPerNode");
 

@@ -17,8 +17,10 @@
 //      V = Q + A^T F + K^T H                   lqr.cpp:715-719       32 + 8
 // Against the 32x32x2 formulation of chain_mf32.hpp the m-row blocks (Z, G, H, K: 8 of 32 rows or
 // columns) cost a 16-wide tile instead of a 32-wide one.  Controls sit at the tile rows / columns
-// row(a & 3, a >> 2): registers 0 and 1 of every lane group, so a contraction over the control index
-// (K = Gn^T H, K^T H) issues two MFMAs per tile, not four.
+// row(a & 3, a >> 2): registers 0 and 1 of every lane group at m <= 8, so a contraction over the control index
+// (K = Gn^T H, K^T H) issues two MFMAs per tile, not four.  The tile has room for 16 controls: m = 12 and m = 16
+// (chain_mt16_wide.hip, the rows of sip_lqr_plan_set_wide_controls) fill registers 0 .. 2 and 0 .. 3 -- VM =
+// ceil(m / 4) MFMAs per contraction, a G sweep of VM steps; every other product is a whole tile at any m.
 //
 // The factorisations are symmetric SWEEPS on the matrix pipe, four pivots per step: with K the pivot
 // set, C = A[:, K], P = A[K, K],
@@ -39,6 +41,8 @@
 // broadcast-FMA sums over the lane groups.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "mt16_launch.hpp"
 
 // Diagnostic build (tools/dev/mt16_stamps.hip): cycles per segment of the backward loop, per wavefront.
 #ifdef SIP_MT16_STAMPS
@@ -392,11 +396,16 @@ __device__ __forceinline__ Mat32<S> load32(const rsrc_t r, const unsigned ocol, 
 #ifndef SIP_MT16_WAVES_F32
 #define SIP_MT16_WAVES_F32 4
 #endif
-template <typename S> struct Waves { static constexpr int value = sizeof(S) == 4 ? SIP_MT16_WAVES_F32 : 2; };
+// The wide rows (M > 8) scale F in the fused fp32 sweep too and have no tuned allocation to protect: they are held to
+// three wavefronts per SIMD in fp32 (168 VGPRs: no scratch at m = 16, 2 dwords at m = 12; the factor sweep fits in 147)
+// and to two in fp64, like the others.
+template <typename S, int M> struct Waves {
+  static constexpr int value = sizeof(S) == 8 ? 2 : M > 8 ? 3 : SIP_MT16_WAVES_F32;
+};
 
 // The fused factor + solve sweep and the factor sweep alone share their text (chain_mt16_sweep_body.hpp).
 template <typename S, int M>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Waves<S>::value, Waves<S>::value)))
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Waves<S, M>::value, Waves<S, M>::value)))
 void chain_factor_solve_mt16(
     const S *__restrict__ mats, const S *__restrict__ vecs, S *__restrict__ sol, S *__restrict__ gains,
     S *__restrict__ wsp, int *__restrict__ status, const long batch, const int T SIP_MT16_STAMP_ARG) {
@@ -409,7 +418,7 @@ void chain_factor_solve_mt16(
 
 // The factor sweep of sip_lqr_plan_set_separate_sweeps: W, K, -G^-1 and the statuses.
 template <typename S, int M>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Waves<S>::value, Waves<S>::value)))
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(Waves<S, M>::value, Waves<S, M>::value)))
 void chain_factor_mt16(const S *__restrict__ mats, S *__restrict__ gains, S *__restrict__ wsp, S *__restrict__ gfac,
                        int *__restrict__ status, const long batch, const int T SIP_MT16_STAMP_ARG) {
   constexpr bool FACTOR = true;
@@ -421,4 +430,31 @@ void chain_factor_mt16(const S *__restrict__ mats, S *__restrict__ gains, S *__r
 }
 
 } // namespace mt16
+
+// The launchers of mt16_launch.hpp for the two kernels above; the units that instantiate them: chain_mt16.hip and
+// chain_mt16_solve.hip (m = 4, 8), chain_mt16_wide.hip and chain_mt16_wide_solve.hip (m = 12, 16).
+#ifndef SIP_MT16_STAMPS
+template <typename S, int M>
+hipError_t launch_mt16(long batch, int T, const void *mats, const void *vecs, void *sol, void *gains,
+                       int32_t *status, void *ws, hipStream_t stream, int /*mode: always the full sweep*/,
+                       void * /*gfac*/) {
+  // 16-byte loads of the stage blocks (fp32, even m) and of the W dump: bases must be 16-byte aligned
+  if (((uintptr_t)mats | (uintptr_t)ws) & 15)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL((mt16::chain_factor_solve_mt16<S, M>), dim3((unsigned)batch), dim3(64), 0, stream,
+                     (const S *)mats, (const S *)vecs, (S *)sol, (S *)gains, (S *)ws, (int *)status, batch, T);
+  return hipGetLastError();
+}
+
+template <typename S, int M>
+hipError_t launch_mt16_factor(long batch, int T, const void *mats, void *gains, int32_t *status, void *ws, void *gfac,
+                              hipStream_t stream) {
+  if (((uintptr_t)mats | (uintptr_t)ws) & 15)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL((mt16::chain_factor_mt16<S, M>), dim3((unsigned)batch), dim3(64), 0, stream, (const S *)mats,
+                     (S *)gains, (S *)ws, (S *)gfac, (int *)status, batch, T);
+  return hipGetLastError();
+}
+#endif
+
 } // namespace sipamd

@@ -7,31 +7,6 @@
 
 namespace sipamd {
 
-template <typename S, int M>
-hipError_t launch_mt16_solve(long batch, int T, const void *mats, const void *vecs_cols, void *sol_cols, void *gains,
-                             void *ws, const void *gfac, void *cws, const int32_t *status, int ncols, long col_stride,
-                             hipStream_t stream) {
-  if (ncols < 1 || ncols > kMt16SolveColumns || (cws == nullptr && ncols != 1))
-    return hipErrorInvalidValue;
-  // 16-byte loads of the stage blocks (fp32, even m) and of the W dump: bases must be 16-byte aligned
-  if (((uintptr_t)mats | (uintptr_t)ws) & 15)
-    return hipErrorInvalidValue;
-  hipLaunchKernelGGL((mt16::chain_solve_mt16<S, M>), dim3((unsigned)batch), dim3(64), 0, stream, (const S *)mats,
-                     (const S *)vecs_cols, (S *)sol_cols, (S *)gains, (S *)ws, (const S *)gfac, (S *)cws,
-                     (const int *)status, batch, T, ncols, col_stride);
-  return hipGetLastError();
-}
-
-template <typename S, int M>
-hipError_t launch_mt16_factor(long batch, int T, const void *mats, void *gains, int32_t *status, void *ws, void *gfac,
-                              hipStream_t stream) {
-  if (((uintptr_t)mats | (uintptr_t)ws) & 15)
-    return hipErrorInvalidValue;
-  hipLaunchKernelGGL((mt16::chain_factor_mt16<S, M>), dim3((unsigned)batch), dim3(64), 0, stream, (const S *)mats,
-                     (S *)gains, (S *)ws, (S *)gfac, (int *)status, batch, T);
-  return hipGetLastError();
-}
-
 static_assert(mt16::Layout<float, 8>::WSN == kMt16SpillPerNode, "the spill the factor sweep left");
 static_assert(mt16_col_workspace_scalars(3, 8, 5) == 4 * 5 * (mt16::N + 8), "cws[node][column][g | k]");
 

@@ -44,7 +44,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
 void chain_solve_mt16(const S *__restrict__ mats, const S *__restrict__ vecs_cols, S *sol_cols, S *gains, S *wsp,
                       const S *__restrict__ gfac, S *cws, const int *__restrict__ status, const long batch,
                       const int T, const int ncols, const long col_stride) {
-  static_assert(M >= 1 && M <= 8, "controls live in registers 0 and 1 of the four lane groups");
+  static_assert(M >= 1 && M <= 16, "controls live in registers 0 .. VM - 1 of the four lane groups: 16 tile rows");
   using TR = Tr<S>;
   using v4 = typename TR::v4;
   using LY = Layout<S, M>;
@@ -353,4 +353,22 @@ void chain_solve_mt16(const S *__restrict__ mats, const S *__restrict__ vecs_col
 }
 
 } // namespace mt16
+
+// The launcher of mt16_launch.hpp for the kernel above (instantiated in chain_mt16_solve.hip and
+// chain_mt16_wide_solve.hip).
+template <typename S, int M>
+hipError_t launch_mt16_solve(long batch, int T, const void *mats, const void *vecs_cols, void *sol_cols, void *gains,
+                             void *ws, const void *gfac, void *cws, const int32_t *status, int ncols, long col_stride,
+                             hipStream_t stream) {
+  if (ncols < 1 || ncols > kMt16SolveColumns || (cws == nullptr && ncols != 1))
+    return hipErrorInvalidValue;
+  // 16-byte loads of the stage blocks (fp32, even m) and of the W dump: bases must be 16-byte aligned
+  if (((uintptr_t)mats | (uintptr_t)ws) & 15)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL((mt16::chain_solve_mt16<S, M>), dim3((unsigned)batch), dim3(64), 0, stream, (const S *)mats,
+                     (const S *)vecs_cols, (S *)sol_cols, (S *)gains, (S *)ws, (const S *)gfac, (S *)cws,
+                     (const int *)status, batch, T, ncols, col_stride);
+  return hipGetLastError();
+}
+
 } // namespace sipamd

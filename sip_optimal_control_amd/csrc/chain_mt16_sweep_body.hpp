@@ -10,7 +10,7 @@
 #ifndef SIP_MT16_SWEEP_BODY
 #error "chain_mt16_sweep_body.hpp is the text of the two kernels of chain_mt16.hpp: include it only where they do"
 #endif
-  static_assert(M >= 1 && M <= 8, "controls live in registers 0 and 1 of the four lane groups");
+  static_assert(M >= 1 && M <= 16, "controls live in registers 0 .. VM - 1 of the four lane groups: 16 tile rows");
 #ifdef SIP_MT16_STAMPS
   unsigned long long seg_[16] = {0}, last_ = __builtin_amdgcn_s_memtime();
   const unsigned long long start_ = last_;
@@ -55,14 +55,15 @@
   auto ldM = [&](const unsigned vo, const unsigned so) { return Mem<S>::ld(rM, vo * ES, so * ES); };
   auto ldV = [&](const unsigned vo, const unsigned so) { return Mem<S>::ld(rV, vo * ES, so * ES); };
 
-  __shared__ S s_v[N], s_t[N], s_g[N], s_sd[N], s_sdi[N], s_x[N], s_z[N], s_gs[16], s_h[8], s_u[8];
+  constexpr int MH = M <= 8 ? 8 : 16; // entries of the control vectors h and u: every control register of the lanes
+  __shared__ S s_v[N], s_t[N], s_g[N], s_sd[N], s_sdi[N], s_x[N], s_z[N], s_gs[16], s_h[MH], s_u[MH];
   constexpr int LDM = TR::ROWS_CONTIGUOUS ? 36 : 33; // column stride of the mirror image (bank spread; 16-byte columns)
   __shared__ __attribute__((aligned(16))) S s_m[N * LDM];
   __shared__ __attribute__((aligned(16))) S s_p[16]; // pivot block of the sweep's current step
 
 
   if constexpr (!FACTOR) {
-    if (L.lane < 8)
+    if (L.lane < MH)
       s_h[L.lane] = S(0), s_u[L.lane] = S(0); // the entries of no control are read as zeros
   }
   int stat = 0;
@@ -129,9 +130,9 @@
     // The factor sweep alone, and the fused sweep in fp64, sweep the unit-diagonal S F S, S = diag(F)^-1/2, and scale
     // back, as the G sweep below does: the sweep's modified operands work against an identity on the pivot block, and
     // the F of a condensed Newton-KKT problem (V ~ J^T R2^-1 J) has a diagonal far from 1.  (A diagonal <= 0 gives a
-    // NaN scale: the sweep then fails, as it must.)  The fp32 fused kernel keeps its sweep of F as it stands: its
-    // register allocation is tuned to the last VGPR.
-    constexpr bool SCALE_F = FACTOR || sizeof(S) == 8;
+    // NaN scale: the sweep then fails, as it must.)  The fp32 fused kernel of m <= 8 keeps its sweep of F as it stands:
+    // its register allocation is tuned to the last VGPR.  The wide rows (m > 8) have no such budget: they scale.
+    constexpr bool SCALE_F = FACTOR || sizeof(S) == 8 || M > 8;
     S fs0 = S(1), fs1 = S(1);
     if constexpr (SCALE_F) {
       S d0 = S(0), d1 = S(0);

@@ -416,6 +416,22 @@ int sip_kkt_plan_set_chain_separate_sweeps(sip_kkt_plan *p, int on) {
   return SIP_LQR_OK;
 }
 
+int sip_kkt_plan_set_chain_wide_controls(sip_kkt_plan *p, int on) {
+  if (p == nullptr || p->theta_dim != 0 || (on && p->chain != nullptr && sip_lqr_has_wide_controls(p->chain)))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  if (!on || p->input_status != SIP_KKT_SUCCESS || p->chain == nullptr)
+    return SIP_LQR_OK; // tree plans: nothing to switch
+  const int rc = sip_lqr_plan_set_wide_controls(p->chain, 1);
+  if (rc != SIP_LQR_OK || !sip_lqr_has_wide_controls(p->chain))
+    return rc; // not a chain of 9 to 16 controls on the general engine: nothing changed
+  // (the Riccati plan keeps no split form -- the general engine had none either -- so the step takes the copy path
+  // n = 32 takes; its workspace, which ends d_work, is now the larger of the two layouts)
+  p->lqr_bytes = std::max(p->lqr_bytes, sip_lqr_workspace_bytes(p->chain));
+  p->ws = kkt::work_offsets(*p);
+  p->name = kkt::plan_name(*p);
+  return SIP_LQR_OK;
+}
+
 int sip_kkt_factor(const sip_kkt_plan *p, const double *d_model, const double *d_w, const double *d_r1,
                    const double *d_r2, const double *d_r3, void *d_work, int32_t *d_status, void *stream) {
   if (p == nullptr || d_status == nullptr)

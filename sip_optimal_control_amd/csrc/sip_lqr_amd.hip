@@ -66,6 +66,9 @@ struct sip_lqr_plan {
   // runs on chain_factor_solve_qf32.  forced_general: SIP_LQR_VARIANT=general at creation, which the opt-in respects
   bool fused_f32 = false;
   bool forced_general = false;
+  // sip_lqr_plan_set_wide_controls on a FULL-layout plan of the general engine with 9 <= m <= 16, n <= 32: the plan
+  // runs on a row of kWideRows, its own (n = 32, m in {12, 16}) or, in fp64, embedded in the one with the least M >= m
+  bool wide_controls = false;
   std::string name_storage;
   Workspace ws;
 
@@ -115,6 +118,14 @@ const KernelEntry kKernels[] = {
 // fp32, n <= 15: four problems per wavefront on v_fmac_f32_dpp (chain_qf32.hpp).  A table of its own that find_kernel
 // never searches: a plan gets one of these rows through sip_lqr_plan_set_fused_f32 alone.
 const KernelEntry kQf32Rows[] = {SIP_QF32_ROWS(QF32_ENTRY)};
+
+// n = 32 on 16 x 16 matrix-core tiles with 12 and 16 controls (chain_mt16_wide.hip, chain_mt16_wide_solve.hip), by
+// ascending M per dtype.  A table of its own that find_kernel and find_embedding_kernel never search: a plan gets one of
+// these rows through sip_lqr_plan_set_wide_controls alone.
+const KernelEntry kWideRows[] = {
+    MT16_ENTRY(SIP_LQR_F32, float, "f32", 12),  MT16_ENTRY(SIP_LQR_F32, float, "f32", 16),
+    MT16_ENTRY(SIP_LQR_F64, double, "f64", 12), MT16_ENTRY(SIP_LQR_F64, double, "f64", 16),
+};
 
 // The dispatch environment, read whenever a plan is created or opted in (tests change it between plans).
 struct DispatchEnv {
@@ -222,7 +233,7 @@ Workspace workspace_layout(const sip_lqr_plan *p) {
 }
 
 // Point the plan at its kernel row (nullptr: the general engine; embedded: a row of a larger shape) and recompute
-// what follows from it.  At creation and again by the fp32 opt-in, after init_generic.
+// what follows from it.  At creation and again by the fp32 and the wide-controls opt-ins, after init_generic.
 void decide_kernel(sip_lqr_plan *p, const KernelEntry *k, bool embedded, const DispatchEnv &env) {
   p->kernel = k;
   p->padded = embedded;
@@ -429,6 +440,27 @@ int sip_lqr_plan_set_fused_f32(sip_lqr_plan *plan, int on) {
 }
 
 int sip_lqr_has_fused_f32(const sip_lqr_plan *plan) { return plan != nullptr && plan->fused_f32 ? 1 : 0; }
+
+int sip_lqr_plan_set_wide_controls(sip_lqr_plan *plan, int on) {
+  if (plan == nullptr || (on && plan->wide_controls))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  if (!on || plan->layout != SIP_LQR_LAYOUT_FULL || plan->kernel != nullptr || plan->forced_general || plan->m < 9 ||
+      plan->m > 16 || plan->n > 32)
+    return SIP_LQR_OK; // not a plan of the general engine with 9 to 16 controls, or one that was asked to stay there
+  const KernelEntry *row = nullptr; // the row of the plan's dtype with the least M >= m
+  for (const KernelEntry &k : kWideRows)
+    if (row == nullptr && k.dtype == plan->dtype && k.m >= plan->m)
+      row = &k;
+  const DispatchEnv env = dispatch_env();
+  const bool exact = plan->n == row->n && plan->m == row->m;
+  if (!exact && (plan->dtype != SIP_LQR_F64 || !env.pad))
+    return SIP_LQR_OK; // the embedding is fp64 only, and SIP_LQR_PAD=0 keeps the general engine, as at creation
+  plan->wide_controls = true;
+  decide_kernel(plan, row, !exact, env);
+  return SIP_LQR_OK;
+}
+
+int sip_lqr_has_wide_controls(const sip_lqr_plan *plan) { return plan != nullptr && plan->wide_controls ? 1 : 0; }
 
 int64_t sip_lqr_plan_batch(const sip_lqr_plan *p) { return p ? p->batch : 0; }
 size_t sip_lqr_scalar_bytes(const sip_lqr_plan *p) { return p ? scalar_size(p) : 0; }

@@ -34,7 +34,7 @@ def _ints(values):
 class BatchedNewtonKKT:
     def __init__(self, parents, children, state_dims, control_dims, node_c_dims=None, node_g_dims=None,
                  edge_c_dims=None, edge_g_dims=None, batch=1, root=0, device="cuda:0", theta_dim=0,
-                 tree_fused=False, chain_separate_sweeps=False):
+                 tree_fused=False, chain_separate_sweeps=False, chain_wide_controls=False):
         self._lib = load_library()
         self.device = resolve_device(device)  # explicit ordinal; raises without a HIP device
         self.E, self.N, self.batch = len(control_dims), len(control_dims) + 1, int(batch)
@@ -48,6 +48,8 @@ class BatchedNewtonKKT:
         self.input_status = self._lib.sip_kkt_input_status(h)
         if tree_fused:  # tree plans: Riccati factor / solve on the split size-class kernels (a no-op elsewhere)
             _check(self._lib.sip_kkt_plan_set_tree_fused(h, 1), "sip_kkt_plan_set_tree_fused")
+        if chain_wide_controls:  # uniform chains with 9 <= m <= 16, n <= 32: the n = 32 kernel for 12 / 16 controls
+            _check(self._lib.sip_kkt_plan_set_chain_wide_controls(h, 1), "sip_kkt_plan_set_chain_wide_controls")
         if chain_separate_sweeps:  # uniform chains on the n = 32 kernel: separate factor / solve sweeps (a no-op elsewhere)
             _check(self._lib.sip_kkt_plan_set_chain_separate_sweeps(h, 1), "sip_kkt_plan_set_chain_separate_sweeps")
         self.x_dim, self.y_dim, self.z_dim, self.model_len = (self._lib.sip_kkt_len(h, k) for k in range(4))
