@@ -310,6 +310,49 @@ int sip_lqr_solve_multi(const sip_lqr_plan *plan, const void *d_mats,
                         void *d_gains, void *d_workspace, void *d_col_workspace,
                         void *stream);
 
+/* The residual of the KKT system the chain entry points solve, evaluated in fp64 on the device (no counterpart in the
+ * reference, whose callers form it on the host), in the vecs layout -- slot q_i, slot c_i, slot r_i:
+ *   rho_q[i] = Q_i x_i - y_i + q_i  (+ M_i u_i + A_i^T y_{i+1}                if i < T)
+ *   rho_c[0] = -x_0 - delta_0 o y_0 + c_0
+ *   rho_c[i] = A_{i-1} x_{i-1} + B_{i-1} u_{i-1} - x_i - delta_i o y_i + c_i     (i >= 1)
+ *   rho_r[i] = M_i^T x_i + R_i u_i + B_i^T y_{i+1} + r_i                       (i < T)
+ * so that a solve whose right-hand side is rho returns the correction d with K (z + d) + b = 0.  Every plan has it
+ * (every dtype, shape, layout and opt-in: it reads `mats` in the plan's layout and nothing of the workspace).  Every
+ * product and sum is fp64 (fused multiply-adds); fp32 mats are widened on load; Q and R are taken symmetric.
+ *   wide = 0: d_vecs and d_sol are in the plan's dtype; wide = 1: they are doubles, with the same per-problem lengths
+ *             (on an SIP_LQR_F64 plan the two are the same thing);
+ *   d_res   : batch * sip_lqr_vecs_len() doubles, or NULL when only the norms are wanted;
+ *   d_norm  : batch doubles, d_norm[p] = max |rho| over problem p (NaN if an entry is).
+ * Kernels only, asynchronous on `stream`.  SIP_LQR_ERR_INVALID_ARGUMENT, before any HIP call: a NULL plan, d_mats,
+ * d_vecs, d_sol or d_norm, or a `wide` that is neither 0 nor 1. */
+int sip_lqr_residual(const sip_lqr_plan *plan, const void *d_mats, const void *d_vecs, const void *d_sol, int wide,
+                     double *d_res, double *d_norm, void *stream);
+
+/* Iterative refinement in fp64 around the plan's own solve, against the factor state of the last sip_lqr_factor() on
+ * d_workspace (the contract of sip_lqr_solve; d_gains is the buffer that call filled).  d_vecs64 (the right-hand
+ * side) and d_sol64 (the iterate, read and written) are doubles with the per-problem lengths of vecs / sol, whatever
+ * the plan's dtype.  `iterations` (1 .. 32) rounds of
+ *   rho / s_p in the plan's dtype, s_p the power of two with s_p <= max |rho| < 2 s_p over problem p (1 when that
+ *             norm is 0 or not finite): exact, and the correction solve stays in range however small rho has become;
+ *   sip_lqr_solve on it (the plan's kernel, opt-ins included);
+ *   sol64 += s_p * d, summed in fp64, skipped where d_status[p] != SIP_LQR_SUCCESS (d_status: the statuses the factor
+ *             call wrote, or NULL: nothing is skipped);
+ * then one more residual.  from_zero = 1: the iterate is zero-filled first, so round 1 is the plan's ordinary solve and
+ * every later round a refinement step; from_zero = 0: d_sol64 holds the starting iterate.
+ *   d_norms : (iterations + 1) * batch doubles; d_norms[j * batch + p] is max |rho| of problem p before round j + 1,
+ *             the last row that of the result;
+ *   d_refine_workspace: sip_lqr_refine_workspace_bytes() of device scratch =
+ *             2 * up(batch * sip_lqr_vecs_len() * sip_lqr_scalar_bytes()) + up(batch * 8), up() rounding up to a
+ *             multiple of 256: rho / s and d in the plan's dtype, then s.
+ * The k part of d_gains is unspecified afterwards (as for sip_lqr_solve_multi); K is untouched.  Kernels only,
+ * asynchronous on `stream`.  SIP_LQR_ERR_INVALID_ARGUMENT, before any HIP call: a NULL plan, d_mats, d_vecs64,
+ * d_sol64, d_workspace, d_refine_workspace or d_norms (d_gains when T > 0), iterations outside 1 .. 32, from_zero
+ * neither 0 nor 1. */
+size_t sip_lqr_refine_workspace_bytes(const sip_lqr_plan *plan);
+int sip_lqr_refine(const sip_lqr_plan *plan, const void *d_mats, const double *d_vecs64, double *d_sol64,
+                   int iterations, int from_zero, void *d_gains, void *d_workspace, void *d_refine_workspace,
+                   const int32_t *d_status, double *d_norms, void *stream);
+
 /* ------------------------------------------------------------------------
  * General trees / per-node dimensions (the full Topology + Dimensions model
  * of lqr.hpp:5-64): the path behind the drop-in C++ `LQR` adapter

@@ -231,6 +231,58 @@ class BatchedChainLQR:
             ctypes.c_void_p(stream.cuda_stream)), "sip_lqr_solve_multi")
         return sol_cols
 
+    def _wide(self, vecs, sol):
+        """0 / 1: `vecs` and `sol` are both in the plan's dtype / both float64 (sip_lqr_residual's `wide`)."""
+        if vecs.dtype != sol.dtype or vecs.dtype not in (self.dtype, torch.float64):
+            raise ValueError(f"vecs and sol: both {self.dtype} or both torch.float64")
+        for t, name in ((vecs, "vecs"), (sol, "sol")):
+            if t.device != self.device or not t.is_contiguous() or t.numel() != self.batch * self.shape.vecs_len:
+                raise ValueError(f"{name}: expected contiguous [{self.batch}, {self.shape.vecs_len}] on {self.device}")
+        return 1 if vecs.dtype == torch.float64 else 0
+
+    def residual(self, mats, vecs, sol, want_vector=True, stream=None):
+        """The residual of the KKT system at `sol`, in fp64 (sip_lqr_residual): (res64 [batch, vecs_len] in the vecs
+        layout, or None with want_vector=False; norm [batch] = max |res| per problem).  vecs and sol: both in the
+        plan's dtype or both float64."""
+        s = self.shape
+        wide = self._wide(vecs, sol)
+        res = torch.empty(self.batch, s.vecs_len, dtype=torch.float64, device=self.device) if want_vector else None
+        norm = torch.empty(self.batch, dtype=torch.float64, device=self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_residual(
+            self._plan, self._ptr(mats, self.batch, s.mats_len, "mats"), ctypes.c_void_p(vecs.data_ptr()),
+            ctypes.c_void_p(sol.data_ptr()), wide, ctypes.c_void_p(res.data_ptr() if want_vector else None),
+            ctypes.c_void_p(norm.data_ptr()), ctypes.c_void_p(stream.cuda_stream)), "sip_lqr_residual")
+        return res, norm
+
+    def refine(self, mats, vecs64, gains, iterations=3, sol=None, use_status=True, stream=None):
+        """Iterative refinement in fp64 around solve(), against the last factor() (sip_lqr_refine): `iterations`
+        rounds of residual -> solve -> update, then one more residual.  vecs64: float64 [batch, vecs_len]; sol: the
+        float64 starting iterate, refined in place, or None to start from zero (round 1 is then the plain solve).
+        Problems whose factor status is not SUCCESS keep their iterate (use_status=False: nothing is skipped).
+        Returns (sol64, norms [iterations + 1, batch]): norms[j] before round j + 1, norms[-1] of the result."""
+        s = self.shape
+        from_zero = sol is None
+        if from_zero:
+            sol = torch.empty(self.batch, s.vecs_len, dtype=torch.float64, device=self.device)
+        if vecs64.dtype != torch.float64 or self._wide(vecs64, sol) != 1:
+            raise ValueError("vecs64 and sol: torch.float64")
+        norms = torch.empty(int(iterations) + 1, self.batch, dtype=torch.float64, device=self.device)
+        if getattr(self, "_refine_ws", None) is None:  # once per plan
+            self._refine_ws = torch.empty(max(1, self._lib.sip_lqr_refine_workspace_bytes(self._plan)),
+                                          dtype=torch.uint8, device=self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_refine(
+            self._plan, self._ptr(mats, self.batch, s.mats_len, "mats"), ctypes.c_void_p(vecs64.data_ptr()),
+            ctypes.c_void_p(sol.data_ptr()), int(iterations), 1 if from_zero else 0,
+            self._ptr(gains, self.batch, s.gains_len, "gains"), ctypes.c_void_p(self.workspace.data_ptr()),
+            ctypes.c_void_p(self._refine_ws.data_ptr()),
+            ctypes.c_void_p(self.status.data_ptr() if use_status else None), ctypes.c_void_p(norms.data_ptr()),
+            ctypes.c_void_p(stream.cuda_stream)), "sip_lqr_refine")
+        return sol, norms
+
     def close(self):
         if getattr(self, "_plan", None):
             self._lib.sip_lqr_plan_destroy(self._plan)

@@ -1,0 +1,45 @@
+// residual_launch.hpp -- the launchers of the KKT residual and of the refinement update on the packed chain layout
+// (chain_residual.hpp, instantiated in chain_residual.hip, a translation unit of its own).  No kernel source in here:
+// the host code (sip_lqr_amd.hip) includes this header alone.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+namespace sipamd {
+namespace residual {
+
+// What one launch of the residual kernel is told.  Buffers are whole-batch device pointers in the packed chain layout
+// of include/sip_lqr_amd.h; lengths are per problem, in scalars.
+struct Args {
+  long batch;
+  int T, n, m;
+  bool f32;       // mats (and the scaled output) are float, else double
+  bool wide;      // vecs and sol are double whatever `f32` says
+  bool symmetric; // SIP_LQR_LAYOUT_SYMMETRIC: Q and R as packed lower triangles
+  const void *mats, *vecs, *sol;
+  // plain form (scaled == nullptr): res may be nullptr; scaled form: rho / s in the plan's dtype, s next to norm
+  double *res;
+  void *scaled;
+  double *scale;
+  double *norm;
+};
+
+// Waves of a workgroup and dynamic LDS bytes of one launch; staged: the stage's blocks go through LDS.
+struct Shape {
+  int waves;
+  bool staged;
+  size_t lds_bytes;
+};
+Shape launch_shape(const Args &a);
+
+hipError_t launch_residual(const Args &a, hipStream_t stream);
+
+// sol64[p] += scale[p] * d[p] (d in the plan's dtype, `len` scalars per problem) where status == nullptr or
+// status[p] == SIP_LQR_SUCCESS
+hipError_t launch_update(long batch, long len, bool f32, const void *d, const double *scale, const int32_t *status,
+                         double *sol64, hipStream_t stream);
+
+} // namespace residual
+} // namespace sipamd

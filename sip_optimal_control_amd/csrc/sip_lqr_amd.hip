@@ -19,6 +19,7 @@
 #include "qf32_launch.hpp"
 #include "generic_plan.hpp"
 #include "qw16_table.hpp"
+#include "residual_launch.hpp"
 #include "stream_fill.hpp"
 
 using sipamd::KernelEntry;
@@ -731,6 +732,89 @@ int sip_lqr_solve_multi(const sip_lqr_plan *plan, const void *d_mats, const void
   }
   return report(e, plan->separate ? "sip_lqr_solve_multi(separate sweeps)" : "sip_lqr_solve_multi");
 }
+
+} // extern "C"
+
+// ---- the residual of the chain KKT system and the refinement around the plan's solve (chain_residual.hpp) ----------
+namespace {
+// The regions of sip_lqr_refine's scratch, in bytes: rho / s and d in the plan's dtype, then s.
+struct RefineWorkspace {
+  size_t rho = 0, d = 0, scale = 0, total = 0;
+};
+RefineWorkspace refine_layout(const sip_lqr_plan *p) {
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t vec = up((size_t)p->batch * (size_t)lens(p).vecs * scalar_size(p));
+  RefineWorkspace w;
+  w.d = vec;
+  w.scale = 2 * vec;
+  w.total = w.scale + up((size_t)p->batch * sizeof(double));
+  return w;
+}
+sipamd::residual::Args residual_args(const sip_lqr_plan *p, const void *mats, const void *vecs, const void *sol,
+                                     bool wide) {
+  sipamd::residual::Args a{};
+  a.batch = (long)p->batch, a.T = p->T, a.n = p->n, a.m = p->m;
+  a.f32 = p->dtype == SIP_LQR_F32;
+  a.wide = wide;
+  a.symmetric = p->layout == SIP_LQR_LAYOUT_SYMMETRIC;
+  a.mats = mats, a.vecs = vecs, a.sol = sol;
+  return a;
+}
+} // namespace
+
+extern "C" {
+
+int sip_lqr_residual(const sip_lqr_plan *plan, const void *d_mats, const void *d_vecs, const void *d_sol, int wide,
+                     double *d_res, double *d_norm, void *stream) {
+  if (plan == nullptr || !d_mats || !d_vecs || !d_sol || !d_norm || (wide != 0 && wide != 1))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  OnPlanDevice on_device(plan, "sip_lqr_residual");
+  if (on_device.rc != SIP_LQR_OK)
+    return on_device.rc;
+  sipamd::residual::Args a = residual_args(plan, d_mats, d_vecs, d_sol, wide == 1);
+  a.res = d_res;
+  a.norm = d_norm;
+  return report(sipamd::residual::launch_residual(a, (hipStream_t)stream), "sip_lqr_residual");
+}
+
+size_t sip_lqr_refine_workspace_bytes(const sip_lqr_plan *plan) { return plan ? refine_layout(plan).total : 0; }
+
+int sip_lqr_refine(const sip_lqr_plan *plan, const void *d_mats, const double *d_vecs64, double *d_sol64,
+                   int iterations, int from_zero, void *d_gains, void *d_workspace, void *d_refine_workspace,
+                   const int32_t *d_status, double *d_norms, void *stream) {
+  if (plan == nullptr || !d_mats || !d_vecs64 || !d_sol64 || !d_workspace || !d_refine_workspace || !d_norms ||
+      (plan->T > 0 && !d_gains) || iterations < 1 || iterations > 32 || (from_zero != 0 && from_zero != 1))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  hipStream_t s = (hipStream_t)stream;
+  OnPlanDevice on_device(plan, "sip_lqr_refine");
+  if (on_device.rc != SIP_LQR_OK)
+    return on_device.rc;
+  const RefineWorkspace f = refine_layout(plan);
+  char *w = (char *)d_refine_workspace;
+  double *scale = (double *)(w + f.scale);
+  const long B = (long)plan->batch, len = lens(plan).vecs;
+  sipamd::residual::Args a = residual_args(plan, d_mats, d_vecs64, d_sol64, true);
+  hipError_t e = from_zero ? sipamd::zero_async(d_sol64, (size_t)B * len * sizeof(double), s) : hipSuccess;
+  for (int j = 0; j < iterations && e == hipSuccess; ++j) {
+    a.scaled = w + f.rho, a.scale = scale, a.norm = d_norms + (size_t)j * B;
+    e = sipamd::residual::launch_residual(a, s);
+    if (e != hipSuccess)
+      break;
+    const int rc = sip_lqr_solve(plan, d_mats, w + f.rho, w + f.d, d_gains, d_workspace, stream);
+    if (rc != SIP_LQR_OK)
+      return rc;
+    e = sipamd::residual::launch_update(B, len, plan->dtype == SIP_LQR_F32, w + f.d, scale, d_status, d_sol64, s);
+  }
+  if (e == hipSuccess) { // the norm of the result
+    a.scaled = nullptr, a.scale = nullptr, a.norm = d_norms + (size_t)iterations * B;
+    e = sipamd::residual::launch_residual(a, s);
+  }
+  return report(e, "sip_lqr_refine");
+}
+
+} // extern "C"
+
+extern "C" {
 
 const char *sip_lqr_kernel_name(const sip_lqr_plan *plan) {
   return plan ? plan->kernel_name : "";
