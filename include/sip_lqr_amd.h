@@ -496,6 +496,61 @@ int sip_lqr_tree_solve_multi(const sip_lqr_tree_plan *plan, const double *d_inpu
                              const int32_t *d_status, void *d_scratch, void *stream);
 const char *sip_lqr_tree_multi_kernel_name(const sip_lqr_tree_plan *plan);
 
+/* The residual of the KKT system the tree entry points solve, evaluated in fp64 on the device (no counterpart in the
+ * reference, whose callers form it on the host; the system is the one of tests/lqr_test.cpp:859-929), for any valid
+ * tree plan -- either engine, dimensions of 0 and a single node included:
+ *   rho_q[i]        = Q_i x_i - y_i + q_i + sum over the child edges e of i, in child_edges order, of
+ *                     (M_e u_e + A_e^T y_child(e))
+ *   rho_c[root]     = -x_root - delta_root o y_root + c_root
+ *   rho_c[child(e)] = A_e x_parent(e) + B_e u_e - x_child - delta_child o y_child + c_child
+ *   rho_r[e]        = M_e^T x_parent(e) + R_e u_e + B_e^T y_child + r_e
+ * in the layout of a right-hand side of sip_lqr_tree_solve_multi (sip_lqr_tree_rhs_len / _offset: rho_q | rho_c where
+ * x | y are, rho_r where u is), so that a solve whose right-hand side is rho returns the correction d with
+ * K (z + d) + b = 0.  Every entry is summed in fp64 as a head + tail pair -- each product's rounding error kept by one
+ * fused multiply-add, each sum's by an error-free transformation -- and rounded once at the end, so it is as accurate
+ * as a sum in twice the working precision: what a refinement round can gain is bounded by what the residual resolves.
+ * Q and R are taken symmetric from their lower triangles; the sum over the children of a node has one order, so two
+ * launches give the same bits.
+ *   d_input : the input arena (its A, B, M, R, Q, delta; q, c, r too when d_rhs is NULL);
+ *   d_rhs   : NULL, or batch * sip_lqr_tree_rhs_len() doubles: q, c, r of every problem, one column;
+ *   d_output: x, y, u in the output arena's layout (only read);
+ *   d_res   : batch * sip_lqr_tree_rhs_len() doubles, or NULL when only the norms are wanted;
+ *   d_norm  : batch doubles, d_norm[p] = max |rho| over problem p (NaN if an entry is).
+ * Nothing of the work arena is read.  sip_lqr_tree_residual_kernel_name(): "tree_residual<staged>/f64" (the matrices
+ * of a node and of an edge go through LDS) or "tree_residual<direct>/f64" (the largest of them exceeds a wavefront's
+ * share of LDS: read in place), decided per plan; a d_input that is not 16-byte aligned is read in place whatever
+ * the name says.  "" for NULL.  Kernels only, asynchronous on `stream`.  SIP_LQR_ERR_INVALID_ARGUMENT, before any HIP
+ * call: a NULL plan or d_norm, a NULL d_input or d_output whose arena is not empty, a latched invalid topology. */
+const char *sip_lqr_tree_residual_kernel_name(const sip_lqr_tree_plan *plan);
+int sip_lqr_tree_residual(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_rhs,
+                          const double *d_output, double *d_res, double *d_norm, void *stream);
+
+/* Iterative refinement in fp64 around the plan's own solve, against the factor state in d_work (left by
+ * sip_lqr_tree_factor(), sip_lqr_tree_factor_fused() or sip_lqr_tree_factor_solve_workspace(); only read).  d_output
+ * is the iterate, read and written.  `iterations` (1 .. 32) rounds of
+ *   rho / s_p, s_p the power of two with s_p <= max |rho| < 2 s_p over problem p (1 when that norm is 0 or not
+ *             finite): exact, and the correction solve stays in range however small rho has become;
+ *   sip_lqr_tree_solve_multi on it with one column (the fused size-class kernel or the general engine, as the plan
+ *             dispatches);
+ *   d_output += s_p * d, summed in fp64, skipped where d_status[p] != SIP_LQR_SUCCESS (d_status: the statuses the
+ *             factor call wrote; required, as the solve skips those problems too);
+ * then one more residual.  from_zero = 1: the iterate is zero-filled first, so round 1 is the plan's ordinary solve and
+ * every later round a refinement step; from_zero = 0: d_output holds the starting iterate.  d_rhs: as for
+ * sip_lqr_tree_residual().
+ *   d_norms : (iterations + 1) * batch doubles; d_norms[j * batch + p] is max |rho| of problem p before round j + 1,
+ *             the last row that of the result;
+ *   d_refine_workspace: sip_lqr_tree_refine_workspace_bytes() of device scratch =
+ *             2 * up(batch * sip_lqr_tree_rhs_len() * 8) + up(batch * 8) +
+ *             up(sip_lqr_tree_solve_multi_scratch_bytes(plan, 1)), up() rounding up to a multiple of 256:
+ *             rho / s, d, s, then the scratch of the one-column solve (0 for NULL or a latched invalid topology).
+ * Kernels only, asynchronous on `stream`.  SIP_LQR_ERR_INVALID_ARGUMENT, before any HIP call: a NULL plan, d_work,
+ * d_status, d_refine_workspace or d_norms, a NULL d_input or d_output whose arena is not empty, iterations outside
+ * 1 .. 32, from_zero neither 0 nor 1, a latched invalid topology. */
+size_t sip_lqr_tree_refine_workspace_bytes(const sip_lqr_tree_plan *plan);
+int sip_lqr_tree_refine(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_work,
+                        const double *d_rhs, double *d_output, int iterations, int from_zero,
+                        const int32_t *d_status, void *d_refine_workspace, double *d_norms, void *stream);
+
 /* Name of the kernel variant the plan dispatches to (static string). */
 const char *sip_lqr_kernel_name(const sip_lqr_plan *plan);
 

@@ -79,6 +79,11 @@ __host__ __device__ inline int image_bytes(const Dims &d, int scalar_bytes) {
 // max that keeps a NaN once it has seen one
 __device__ __forceinline__ double nan_max(const double a, const double b) { return (b > a || b != b) ? b : a; }
 
+// The scale of a refinement round: the power of two with s <= norm < 2 s; 1 for a norm that is 0 or not finite.
+__device__ __forceinline__ double pow2_scale(const double norm) {
+  return (norm > 0.0 && norm < __builtin_huge_val()) ? ldexp(1.0, ilogb(norm)) : 1.0;
+}
+
 // (row, col) of a lower triangle packed by columns, row >= col
 __device__ __forceinline__ int tri(const int row, const int col, const int dim) {
   return col * dim - col * (col - 1) / 2 + (row - col);
@@ -254,9 +259,7 @@ __global__ void __launch_bounds__(kLanes * kMaxWaves)
       double all = red[0];
       for (int k = 1; k < waves; ++k)
         all = nan_max(all, red[k]);
-      // the power of two with s_p <= norm < 2 s_p; 1 for a norm that is 0 or not finite
-      if (all > 0.0 && all < __builtin_huge_val())
-        s_p = ldexp(1.0, ilogb(all));
+      s_p = pow2_scale(all);
       if (threadIdx.x == 0) {
         norm[p] = all;
         if (scaled != nullptr)

@@ -12,8 +12,10 @@
 #include <vector>
 
 #include "generic_plan.hpp"
+#include "residual_launch.hpp"
 #include "table_packer.hpp"
 #include "tree_plan.hpp"
+#include "tree_residual_launch.hpp"
 
 struct sip_lqr_tree_plan {
   int64_t batch = 0;
@@ -25,6 +27,7 @@ struct sip_lqr_tree_plan {
   sipamd::TreeSchedule sched{};
   void *d_steps = nullptr;
   sipamd::TreeScratch scratch; // of the fused kernels: padded gains at 0, then the spill
+  sipamd::residual::TreeShape residual; // of the residual kernel: staged or in place, wavefronts, LDS
   ~sip_lqr_tree_plan() {
     if (d_steps != nullptr)
       (void)hipFree(d_steps);
@@ -107,6 +110,8 @@ int sip_lqr_tree_plan_create(int64_t batch, int num_edges, int root,
   // layout, upload
   g.layout_tree_native();
   hipError_t e = g.upload(device);
+  p->residual = sipamd::residual::tree_launch_shape(N, E, g.state_dims.data(), g.control_dims.data(), g.parents.data(),
+                                                    g.children.data());
   // size class of the fused kernels; where one holds the tree: its schedule and its scratch
   if (e == hipSuccess)
     p->fused = sipamd::choose_tree_class(g);
@@ -316,6 +321,88 @@ const char *sip_lqr_tree_split_kernel_name(const sip_lqr_tree_plan *plan) {
   if (plan == nullptr)
     return "";
   return plan->fused != nullptr ? plan->fused->split_name : "tree_generic/f64";
+}
+
+// ---- the residual of the tree KKT system and the refinement around the plan's solve (tree_residual.hpp) -----------
+} // extern "C"
+
+namespace {
+// The regions of sip_lqr_tree_refine's scratch, in bytes: rho / s, d, s, then the scratch of the one-column solve.
+struct TreeRefineWorkspace {
+  size_t d = 0, scale = 0, solve = 0, total = 0; // rho / s is at 0
+};
+TreeRefineWorkspace tree_refine_layout(const sip_lqr_tree_plan *p) {
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t vec = up((size_t)p->batch * (size_t)p->g.out_len * sizeof(double));
+  TreeRefineWorkspace w;
+  w.d = vec;
+  w.scale = 2 * vec;
+  w.solve = w.scale + up((size_t)p->batch * sizeof(double));
+  w.total = w.solve + up(sip_lqr_tree_solve_multi_scratch_bytes(p, 1));
+  return w;
+}
+} // namespace
+
+extern "C" {
+
+const char *sip_lqr_tree_residual_kernel_name(const sip_lqr_tree_plan *plan) {
+  if (plan == nullptr)
+    return "";
+  return plan->residual.staged ? "tree_residual<staged>/f64" : "tree_residual<direct>/f64";
+}
+
+int sip_lqr_tree_residual(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_rhs,
+                          const double *d_output, double *d_res, double *d_norm, void *stream) {
+  if (plan == nullptr || d_norm == nullptr || missing_input(plan, d_input) || missing_output(plan, d_output) ||
+      plan->topology_status != SIP_LQR_SUCCESS)
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  OnPlanDevice dev(plan, stream);
+  if (dev.rc != SIP_LQR_OK)
+    return dev.rc;
+  sipamd::residual::TreeArgs a{};
+  a.batch = (long)plan->batch, a.input = d_input, a.rhs = d_rhs, a.sol = d_output;
+  a.res = d_res, a.norm = d_norm;
+  return report(sipamd::residual::launch_tree_residual(plan->g.meta, plan->residual, a, dev.s),
+                "sip_lqr_tree_residual");
+}
+
+size_t sip_lqr_tree_refine_workspace_bytes(const sip_lqr_tree_plan *plan) {
+  return plan != nullptr && plan->topology_status == SIP_LQR_SUCCESS ? tree_refine_layout(plan).total : 0;
+}
+
+int sip_lqr_tree_refine(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_work, const double *d_rhs,
+                        double *d_output, int iterations, int from_zero, const int32_t *d_status,
+                        void *d_refine_workspace, double *d_norms, void *stream) {
+  if (plan == nullptr || d_status == nullptr || d_work == nullptr || d_refine_workspace == nullptr ||
+      d_norms == nullptr || missing_input(plan, d_input) || missing_output(plan, d_output) || iterations < 1 ||
+      iterations > 32 || (from_zero != 0 && from_zero != 1) || plan->topology_status != SIP_LQR_SUCCESS)
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  OnPlanDevice dev(plan, stream);
+  if (dev.rc != SIP_LQR_OK)
+    return dev.rc;
+  const TreeRefineWorkspace f = tree_refine_layout(plan);
+  char *w = (char *)d_refine_workspace;
+  double *rho = (double *)w, *d = (double *)(w + f.d), *scale = (double *)(w + f.scale);
+  const long B = (long)plan->batch, len = plan->g.out_len;
+  sipamd::residual::TreeArgs a{};
+  a.batch = B, a.input = d_input, a.rhs = d_rhs, a.sol = d_output;
+  hipError_t e = from_zero ? sipamd::zero_async(d_output, (size_t)B * len * sizeof(double), dev.s) : hipSuccess;
+  for (int j = 0; j < iterations && e == hipSuccess; ++j) {
+    a.scaled = rho, a.scale = scale, a.norm = d_norms + (size_t)j * B;
+    e = sipamd::residual::launch_tree_residual(plan->g.meta, plan->residual, a, dev.s);
+    if (e != hipSuccess)
+      break;
+    // (an empty output arena: rho and d have no entries, and the solve's check of them does not apply)
+    const int rc = sip_lqr_tree_solve_multi(plan, d_input, d_work, rho, d, 1, d_status, w + f.solve, stream);
+    if (rc != SIP_LQR_OK)
+      return rc;
+    e = sipamd::residual::launch_update(B, len, false, d, scale, d_status, d_output, dev.s);
+  }
+  if (e == hipSuccess) { // the norm of the result
+    a.scaled = nullptr, a.scale = nullptr, a.norm = d_norms + (size_t)iterations * B;
+    e = sipamd::residual::launch_tree_residual(plan->g.meta, plan->residual, a, dev.s);
+  }
+  return report(e, "sip_lqr_tree_refine");
 }
 
 } // extern "C"

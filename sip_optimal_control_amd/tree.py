@@ -196,6 +196,60 @@ class BatchedTreeLQR:
                                                   ctypes.c_void_p(s.cuda_stream)), "sip_lqr_tree_solve_multi")
         return out_cols
 
+    @property
+    def residual_kernel_name(self):
+        return self._lib.sip_lqr_tree_residual_kernel_name(self._plan).decode()
+
+    def _rhs_ptr(self, rhs):
+        """One column of right-hand sides (batch, rhs_len) float64 on the device, or None: q, c, r of `input`."""
+        if rhs is None:
+            return None
+        if rhs.dtype != torch.float64 or not rhs.is_contiguous() or rhs.numel() != self.batch * max(1, self.rhs_len):
+            raise ValueError("rhs: contiguous torch.float64 of (batch, rhs_len)")
+        return ctypes.c_void_p(rhs.data_ptr())
+
+    def residual(self, output=None, rhs=None, want_vector=True):
+        """The residual of the KKT system at `output` (default: self.output), in fp64 (sip_lqr_tree_residual):
+        (res [batch, rhs_len] in the layout of a right-hand side of solve_multi, or None with want_vector=False;
+        norm [batch] = max |res| per problem).  rhs: one column (batch, rhs_len) in place of q, c, r of `input`."""
+        output = self.output if output is None else output
+        res = torch.empty(self.batch, max(1, self.rhs_len), dtype=torch.float64, device=self.device) \
+            if want_vector else None
+        norm = torch.empty(self.batch, dtype=torch.float64, device=self.device)
+        s = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_tree_residual(self._plan, ctypes.c_void_p(self.input.data_ptr()), self._rhs_ptr(rhs),
+                                               ctypes.c_void_p(output.data_ptr()),
+                                               ctypes.c_void_p(res.data_ptr() if want_vector else None),
+                                               ctypes.c_void_p(norm.data_ptr()),
+                                               ctypes.c_void_p(s.cuda_stream)), "sip_lqr_tree_residual")
+        return res, norm
+
+    def refine(self, iterations=2, rhs=None, output=None):
+        """Iterative refinement in fp64 around the plan's solve, against the factor state in `work` (left by factor(),
+        factor_fused() or factor_solve(workspace=True)) (sip_lqr_tree_refine): `iterations` rounds of residual ->
+        one-column solve -> update, then one more residual.  output: the starting iterate (batch, output_len),
+        refined in place, or None: from zero into self.output (round 1 is then the plain solve).  Problems whose
+        status is not SUCCESS keep their iterate.  Returns (output, norms [iterations + 1, batch]): norms[j] before
+        round j + 1, norms[-1] of the result."""
+        from_zero = output is None
+        if from_zero:
+            output = self.output
+        if output.dtype != torch.float64 or not output.is_contiguous():
+            raise ValueError("output: contiguous torch.float64")
+        norms = torch.empty(int(iterations) + 1, self.batch, dtype=torch.float64, device=self.device)
+        need = self._lib.sip_lqr_tree_refine_workspace_bytes(self._plan)
+        if getattr(self, "_refine_scratch", None) is None or self._refine_scratch.numel() < need:
+            self._refine_scratch = torch.empty(max(1, need), dtype=torch.uint8, device=self.device)
+        s = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_tree_refine(self._plan, ctypes.c_void_p(self.input.data_ptr()),
+                                             ctypes.c_void_p(self.work.data_ptr()), self._rhs_ptr(rhs),
+                                             ctypes.c_void_p(output.data_ptr()), int(iterations),
+                                             1 if from_zero else 0, ctypes.c_void_p(self.status.data_ptr()),
+                                             ctypes.c_void_p(self._refine_scratch.data_ptr()),
+                                             ctypes.c_void_p(norms.data_ptr()),
+                                             ctypes.c_void_p(s.cuda_stream)), "sip_lqr_tree_refine")
+        return output, norms
+
     def unpack_solution(self, b=0, output=None):
         out = (self.output[b] if output is None else output[b]).cpu().numpy()
         x, y, u = [], [], []
