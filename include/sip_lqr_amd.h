@@ -297,9 +297,10 @@ int sip_lqr_solve(const sip_lqr_plan *plan, const void *d_mats,
  * Schur complement, helpers.cpp:387) against the factor state of the last
  * sip_lqr_factor() on the same workspace.  d_vecs_cols / d_sol_cols: num_rhs
  * arrays of sip_lqr_vecs_bytes() each, one after the other (column c at
- * c * sip_lqr_vecs_bytes()).  Shapes with a multi-rhs kernel (the fp64 shapes of
- * the reference's benchmark grid) carry up to 8 columns through ONE backward /
- * forward sweep, fetching every matrix operand of a stage once;
+ * c * sip_lqr_vecs_bytes()).  Shapes with a multi-rhs kernel (every fp64 shape
+ * n <= 16, m <= 8) carry up to 8 columns through ONE backward / forward sweep,
+ * fetching every matrix operand of a stage once; plans with the separate sweeps
+ * carry 8 (fp32, n <= 15) or 16 (n = 32) columns per launch;
  * d_col_workspace: sip_lqr_solve_multi_workspace_bytes() of device scratch
  * (per-column g, h, k of the rollout).  Other shapes run sip_lqr_solve() per
  * column (workspace bytes 0, d_col_workspace may be NULL).  The k part of

@@ -263,6 +263,25 @@ def test_cases_reach_every_rule(printed):
     assert by_name["single node"]["class"]["n"] == 4
 
 
+def test_every_size_class_is_in_the_multi_column_gpu_test():
+    """The TREE_CLASS(N, M) list of csrc/tree_qw16.hip, read from the source, is the list this file states and the
+    list tests/test_gpu_tree_multi.py runs with more than one column: a new class cannot arrive untested.  Each
+    enumerated case lands in its own class and not in a cheaper one."""
+    import os
+    import re
+    import test_gpu_tree_multi as multi
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "sip_optimal_control_amd", "csrc", "tree_qw16.hip")) as f:
+        text = f.read()
+    (table,) = re.findall(r"kClasses\[\]\s*=\s*\{(.*?)\};", text, flags=re.S)
+    in_source = [(int(n), int(m)) for n, m in re.findall(r"TREE_CLASS\(\s*(\d+)\s*,\s*(\d+)\s*\)", table)]
+    assert len(in_source) == len(set(in_source)) and in_source == CLASSES
+    assert [(n, m) for n, m, _ in multi.CLASSES] == in_source
+    for max_n, max_m, tag in multi.CLASSES:
+        first = [(n, m) for n, m in in_source if n >= max_n and m >= max_m][0]
+        assert tag == "<%d,%d>" % first == "<%d,%d>" % (max_n, max_m)
+
+
 def test_chain_layout(printed):
     n, m, T = CHAIN_LAYOUT
     got = printed[-1]
