@@ -354,6 +354,48 @@ int sip_lqr_refine(const sip_lqr_plan *plan, const void *d_mats, const double *d
                    int iterations, int from_zero, void *d_gains, void *d_workspace, void *d_refine_workspace,
                    const int32_t *d_status, double *d_norms, void *stream);
 
+/* sip_lqr_residual for several right-hand sides and iterates against one d_mats, the columns laid out as for
+ * sip_lqr_solve_multi: column c of d_vecs_cols, d_sol_cols and d_res_cols is a whole-batch array at
+ * c * batch * sip_lqr_vecs_len() scalars.  One launch stages a stage's blocks once and carries
+ * sip_lqr_residual_multi_columns() columns through them (1 .. 8, by the shape and dtype of the plan, for a d_mats
+ * that is 16-byte aligned; 0 for a NULL plan); the columns go in groups of that many, one launch per group.  Column c
+ * is bit for bit what sip_lqr_residual computes on that column.  Formulas, `wide`, the dtype rules and "every plan has
+ * it" are those of sip_lqr_residual.
+ *   d_res_cols: num_rhs * batch * sip_lqr_vecs_len() doubles, or NULL when only the norms are wanted;
+ *   d_norms   : num_rhs * batch doubles, d_norms[c * batch + p] = max |rho| over problem p in column c.
+ * num_rhs = 0 launches nothing.  Kernels only, asynchronous on `stream`.  SIP_LQR_ERR_INVALID_ARGUMENT, before any HIP
+ * call: a NULL plan, d_mats or d_norms, num_rhs < 0, num_rhs > 0 with a NULL d_vecs_cols or d_sol_cols, or a `wide`
+ * that is neither 0 nor 1. */
+int sip_lqr_residual_multi_columns(const sip_lqr_plan *plan);
+int sip_lqr_residual_multi(const sip_lqr_plan *plan, const void *d_mats, const void *d_vecs_cols,
+                           const void *d_sol_cols, int num_rhs, int wide, double *d_res_cols, double *d_norms,
+                           void *stream);
+
+/* sip_lqr_refine for several right-hand sides: the contract of sip_lqr_refine per column, the columns of d_vecs64_cols
+ * and d_sol64_cols laid out as above (doubles).  `iterations` (1 .. 32) rounds of
+ *   the scaled residual of all columns (sip_lqr_residual_multi's kernel), rho / s_{p,c} in the plan's dtype with one
+ *             power of two per problem AND column, never one shared by the columns of a problem;
+ *   sip_lqr_solve_multi on all num_rhs columns (whatever the plan runs: column sweeps, opt-ins, embedding, or column
+ *             by column on the general engine);
+ *   sol64[c][p] += s_{p,c} * d[c][p], skipped in every column where d_status[p] != SIP_LQR_SUCCESS (d_status: per
+ *             problem, the statuses the factor call wrote, or NULL: nothing is skipped);
+ * then one more residual of all columns.  from_zero as for sip_lqr_refine.
+ *   d_norms : (iterations + 1) * num_rhs * batch doubles; d_norms[(j * num_rhs + c) * batch + p] is max |rho| of
+ *             problem p in column c before round j + 1, the last row that of the result;
+ *   d_col_workspace: sip_lqr_solve_multi_workspace_bytes(plan, num_rhs) of device scratch; may be NULL where that is 0;
+ *   d_refine_workspace: sip_lqr_refine_multi_workspace_bytes(plan, num_rhs) of device scratch =
+ *             2 * up(num_rhs * batch * sip_lqr_vecs_len() * sip_lqr_scalar_bytes()) + up(num_rhs * batch * 8), up()
+ *             rounding up to a multiple of 256: rho / s, then d, both [num_rhs][batch][vecs_len] in the plan's dtype
+ *             (sip_lqr_solve_multi's column arrays as they stand), then s[c][p]; 0 for a NULL plan or num_rhs < 1.
+ * num_rhs = 0 launches nothing.  The k part of d_gains is unspecified afterwards; K is untouched.  Kernels only, no
+ * allocation and no synchronisation, asynchronous on `stream`.  SIP_LQR_ERR_INVALID_ARGUMENT, before any HIP call:
+ * what sip_lqr_refine rejects, num_rhs < 0, or a NULL d_col_workspace where its bytes are not 0. */
+size_t sip_lqr_refine_multi_workspace_bytes(const sip_lqr_plan *plan, int num_rhs);
+int sip_lqr_refine_multi(const sip_lqr_plan *plan, const void *d_mats, const double *d_vecs64_cols,
+                         double *d_sol64_cols, int num_rhs, int iterations, int from_zero, void *d_gains,
+                         void *d_workspace, void *d_col_workspace, void *d_refine_workspace,
+                         const int32_t *d_status, double *d_norms, void *stream);
+
 /* ------------------------------------------------------------------------
  * General trees / per-node dimensions (the full Topology + Dimensions model
  * of lqr.hpp:5-64): the path behind the drop-in C++ `LQR` adapter

@@ -283,6 +283,72 @@ class BatchedChainLQR:
             ctypes.c_void_p(stream.cuda_stream)), "sip_lqr_refine")
         return sol, norms
 
+    @property
+    def residual_multi_columns(self):
+        """Columns one launch of residual_multi carries on this plan (sip_lqr_residual_multi_columns)."""
+        return int(self._lib.sip_lqr_residual_multi_columns(self._plan))
+
+    def _cols(self, t, name, dtypes):
+        """num_rhs of a contiguous [num_rhs, batch, vecs_len] column array on the plan's device."""
+        if t.dtype not in dtypes or t.device != self.device or not t.is_contiguous() or t.dim() != 3 \
+                or tuple(t.shape[1:]) != (self.batch, self.shape.vecs_len):
+            raise ValueError(f"{name}: expected contiguous {' or '.join(map(str, dtypes))} "
+                             f"[num_rhs, {self.batch}, {self.shape.vecs_len}] on {self.device}")
+        return int(t.shape[0])
+
+    def residual_multi(self, mats, vecs_cols, sol_cols, want_vector=True, stream=None):
+        """residual() for several right-hand sides and iterates against one `mats` (sip_lqr_residual_multi):
+        vecs_cols / sol_cols are [num_rhs, batch, vecs_len], both in the plan's dtype or both float64.  Returns
+        (res64 [num_rhs, batch, vecs_len], or None with want_vector=False; norms [num_rhs, batch]).  Column c is bit
+        for bit residual() on that column."""
+        s = self.shape
+        num_rhs = self._cols(vecs_cols, "vecs_cols", (self.dtype, torch.float64))
+        if self._cols(sol_cols, "sol_cols", (vecs_cols.dtype,)) != num_rhs:
+            raise ValueError("sol_cols: as many columns as vecs_cols")
+        wide = 1 if vecs_cols.dtype == torch.float64 else 0
+        res = torch.empty(num_rhs, self.batch, s.vecs_len, dtype=torch.float64, device=self.device) \
+            if want_vector else None
+        norms = torch.empty(num_rhs, self.batch, dtype=torch.float64, device=self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_residual_multi(
+            self._plan, self._ptr(mats, self.batch, s.mats_len, "mats"), ctypes.c_void_p(vecs_cols.data_ptr()),
+            ctypes.c_void_p(sol_cols.data_ptr()), num_rhs, wide,
+            ctypes.c_void_p(res.data_ptr() if want_vector else None), ctypes.c_void_p(norms.data_ptr()),
+            ctypes.c_void_p(stream.cuda_stream)), "sip_lqr_residual_multi")
+        return res, norms
+
+    def refine_multi(self, mats, vecs64_cols, gains, iterations=3, sol_cols=None, use_status=True, stream=None):
+        """refine() for several right-hand sides around solve_multi(), against the last factor()
+        (sip_lqr_refine_multi): vecs64_cols float64 [num_rhs, batch, vecs_len]; sol_cols the float64 starting
+        iterates, refined in place, or None to start from zero.  A problem whose factor status is not SUCCESS keeps
+        its iterate in every column (use_status=False: nothing is skipped).  Returns (sol64_cols, norms
+        [iterations + 1, num_rhs, batch])."""
+        s = self.shape
+        num_rhs = self._cols(vecs64_cols, "vecs64_cols", (torch.float64,))
+        from_zero = sol_cols is None
+        if from_zero:
+            sol_cols = torch.empty(num_rhs, self.batch, s.vecs_len, dtype=torch.float64, device=self.device)
+        if self._cols(sol_cols, "sol_cols", (torch.float64,)) != num_rhs:
+            raise ValueError("sol_cols: as many columns as vecs64_cols")
+        norms = torch.empty(int(iterations) + 1, num_rhs, self.batch, dtype=torch.float64, device=self.device)
+        need = self._lib.sip_lqr_refine_multi_workspace_bytes(self._plan, num_rhs)
+        if getattr(self, "_refine_multi_ws", None) is None or self._refine_multi_ws.numel() < need:  # grows with num_rhs
+            self._refine_multi_ws = torch.empty(max(1, need), dtype=torch.uint8, device=self.device)
+        need = self._lib.sip_lqr_solve_multi_workspace_bytes(self._plan, num_rhs)
+        if getattr(self, "_col_ws", None) is None or self._col_ws.numel() < need:
+            self._col_ws = torch.empty(max(1, need), dtype=torch.uint8, device=self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_refine_multi(
+            self._plan, self._ptr(mats, self.batch, s.mats_len, "mats"), ctypes.c_void_p(vecs64_cols.data_ptr()),
+            ctypes.c_void_p(sol_cols.data_ptr()), num_rhs, int(iterations), 1 if from_zero else 0,
+            self._ptr(gains, self.batch, s.gains_len, "gains"), ctypes.c_void_p(self.workspace.data_ptr()),
+            ctypes.c_void_p(self._col_ws.data_ptr()), ctypes.c_void_p(self._refine_multi_ws.data_ptr()),
+            ctypes.c_void_p(self.status.data_ptr() if use_status else None), ctypes.c_void_p(norms.data_ptr()),
+            ctypes.c_void_p(stream.cuda_stream)), "sip_lqr_refine_multi")
+        return sol_cols, norms
+
     def close(self):
         if getattr(self, "_plan", None):
             self._lib.sip_lqr_plan_destroy(self._plan)

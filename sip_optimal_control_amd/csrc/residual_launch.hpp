@@ -7,6 +7,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "residual_cols_shape.hpp"
+
 namespace sipamd {
 namespace residual {
 
@@ -40,6 +42,17 @@ hipError_t launch_residual(const Args &a, hipStream_t stream);
 // status[p] == SIP_LQR_SUCCESS
 hipError_t launch_update(long batch, long len, bool f32, const void *d, const double *scale, const int32_t *status,
                          double *sol64, hipStream_t stream);
+
+// The column form (chain_residual_cols.hpp, instantiated in chain_residual_cols.hip).  `a` describes column 0: vecs,
+// sol, res and scaled are [num_cols][batch][vecs_len] arrays (sip_lqr_solve_multi's layout), norm and scale
+// [num_cols][batch].  The columns go in groups of cols_launch_shape(a, kColsMax).columns, one launch per group, a
+// short last group on the least instantiation that holds it.
+ColsShape cols_launch_shape(const Args &a, int requested);
+hipError_t launch_residual_cols(const Args &a, int num_cols, hipStream_t stream);
+
+// sol64[c][p] += scale[c][p] * d[c][p] where status == nullptr or status[p] == SIP_LQR_SUCCESS (status per problem)
+hipError_t launch_update_cols(long cols, long batch, long len, bool f32, const void *d, const double *scale,
+                              const int32_t *status, double *sol64, hipStream_t stream);
 
 } // namespace residual
 } // namespace sipamd

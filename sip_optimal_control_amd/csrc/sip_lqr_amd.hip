@@ -814,6 +814,95 @@ int sip_lqr_refine(const sip_lqr_plan *plan, const void *d_mats, const double *d
 
 } // extern "C"
 
+// ---- the same for several columns (chain_residual_cols.hpp) ---------------------------------------------------------
+namespace {
+// sip_lqr_refine_multi's scratch: rho / s and d as [num_rhs][batch][vecs_len] in the plan's dtype, then s[c][p].
+RefineWorkspace refine_multi_layout(const sip_lqr_plan *p, int num_rhs) {
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t cols = num_rhs < 1 ? 0 : (size_t)num_rhs;
+  const size_t vec = up(cols * (size_t)p->batch * (size_t)lens(p).vecs * scalar_size(p));
+  RefineWorkspace w;
+  w.d = vec;
+  w.scale = 2 * vec;
+  w.total = w.scale + up(cols * (size_t)p->batch * sizeof(double));
+  return w;
+}
+} // namespace
+
+extern "C" {
+
+int sip_lqr_residual_multi_columns(const sip_lqr_plan *plan) {
+  if (plan == nullptr)
+    return 0;
+  return sipamd::residual::cols_shape(plan->n, plan->m, plan->T, plan->dtype == SIP_LQR_F32,
+                                      plan->layout == SIP_LQR_LAYOUT_SYMMETRIC, true, sipamd::residual::kColsMax)
+      .columns;
+}
+
+int sip_lqr_residual_multi(const sip_lqr_plan *plan, const void *d_mats, const void *d_vecs_cols,
+                           const void *d_sol_cols, int num_rhs, int wide, double *d_res_cols, double *d_norms,
+                           void *stream) {
+  if (plan == nullptr || !d_mats || !d_norms || num_rhs < 0 || (num_rhs > 0 && (!d_vecs_cols || !d_sol_cols)) ||
+      (wide != 0 && wide != 1))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  if (num_rhs == 0)
+    return SIP_LQR_OK;
+  OnPlanDevice on_device(plan, "sip_lqr_residual_multi");
+  if (on_device.rc != SIP_LQR_OK)
+    return on_device.rc;
+  sipamd::residual::Args a = residual_args(plan, d_mats, d_vecs_cols, d_sol_cols, wide == 1);
+  a.res = d_res_cols;
+  a.norm = d_norms;
+  return report(sipamd::residual::launch_residual_cols(a, num_rhs, (hipStream_t)stream), "sip_lqr_residual_multi");
+}
+
+size_t sip_lqr_refine_multi_workspace_bytes(const sip_lqr_plan *plan, int num_rhs) {
+  return plan ? refine_multi_layout(plan, num_rhs).total : 0;
+}
+
+int sip_lqr_refine_multi(const sip_lqr_plan *plan, const void *d_mats, const double *d_vecs64_cols,
+                         double *d_sol64_cols, int num_rhs, int iterations, int from_zero, void *d_gains,
+                         void *d_workspace, void *d_col_workspace, void *d_refine_workspace,
+                         const int32_t *d_status, double *d_norms, void *stream) {
+  if (plan == nullptr || !d_mats || !d_vecs64_cols || !d_sol64_cols || !d_workspace || !d_refine_workspace ||
+      !d_norms || (plan->T > 0 && !d_gains) || iterations < 1 || iterations > 32 ||
+      (from_zero != 0 && from_zero != 1) || num_rhs < 0 ||
+      (!d_col_workspace && sip_lqr_solve_multi_workspace_bytes(plan, num_rhs) > 0))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  if (num_rhs == 0)
+    return SIP_LQR_OK;
+  hipStream_t s = (hipStream_t)stream;
+  OnPlanDevice on_device(plan, "sip_lqr_refine_multi");
+  if (on_device.rc != SIP_LQR_OK)
+    return on_device.rc;
+  const RefineWorkspace f = refine_multi_layout(plan, num_rhs);
+  char *w = (char *)d_refine_workspace;
+  double *scale = (double *)(w + f.scale);
+  const long B = (long)plan->batch, len = lens(plan).vecs;
+  const size_t row = (size_t)num_rhs * B; // norms of one round
+  sipamd::residual::Args a = residual_args(plan, d_mats, d_vecs64_cols, d_sol64_cols, true);
+  hipError_t e = from_zero ? sipamd::zero_async(d_sol64_cols, row * len * sizeof(double), s) : hipSuccess;
+  for (int j = 0; j < iterations && e == hipSuccess; ++j) {
+    a.scaled = w + f.rho, a.scale = scale, a.norm = d_norms + (size_t)j * row;
+    e = sipamd::residual::launch_residual_cols(a, num_rhs, s);
+    if (e != hipSuccess)
+      break;
+    const int rc =
+        sip_lqr_solve_multi(plan, d_mats, w + f.rho, w + f.d, num_rhs, d_gains, d_workspace, d_col_workspace, stream);
+    if (rc != SIP_LQR_OK)
+      return rc;
+    e = sipamd::residual::launch_update_cols(num_rhs, B, len, plan->dtype == SIP_LQR_F32, w + f.d, scale, d_status,
+                                             d_sol64_cols, s);
+  }
+  if (e == hipSuccess) { // the norms of the result
+    a.scaled = nullptr, a.scale = nullptr, a.norm = d_norms + (size_t)iterations * row;
+    e = sipamd::residual::launch_residual_cols(a, num_rhs, s);
+  }
+  return report(e, "sip_lqr_refine_multi");
+}
+
+} // extern "C"
+
 extern "C" {
 
 const char *sip_lqr_kernel_name(const sip_lqr_plan *plan) {
