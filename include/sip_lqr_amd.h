@@ -594,6 +594,50 @@ int sip_lqr_tree_refine(const sip_lqr_tree_plan *plan, const double *d_input, co
                         const double *d_rhs, double *d_output, int iterations, int from_zero,
                         const int32_t *d_status, void *d_refine_workspace, double *d_norms, void *stream);
 
+/* sip_lqr_tree_residual for several right-hand sides and iterates against one d_input, the columns laid out as for
+ * sip_lqr_tree_solve_multi: column c of d_rhs_cols, d_out_cols and d_res_cols is a whole-batch array at
+ * c * batch * sip_lqr_tree_rhs_len() scalars.  One launch handles the matrices of a node or an edge once and carries
+ * sip_lqr_tree_residual_multi_columns() columns through them (1 .. 8, by the topology and dimensions of the plan, for
+ * a d_input that is 16-byte aligned; 0 for a NULL plan or a latched invalid topology); the columns go in groups of
+ * that many, one launch per group, a group of one column on the kernel of sip_lqr_tree_residual.  Column c is bit for
+ * bit what sip_lqr_tree_residual computes on that column.
+ *   d_rhs_cols: NULL (q, c, r of d_input for every column), or num_rhs * batch * sip_lqr_tree_rhs_len() doubles;
+ *   d_out_cols: num_rhs * batch * sip_lqr_tree_rhs_len() doubles, x, y, u of every column (only read);
+ *   d_res_cols: num_rhs * batch * sip_lqr_tree_rhs_len() doubles, or NULL when only the norms are wanted;
+ *   d_norms   : num_rhs * batch doubles, d_norms[c * batch + p] = max |rho| over problem p in column c.
+ * sip_lqr_tree_residual_multi_kernel_name(): "tree_residual_cols<staged,NC>/f64" or "tree_residual_cols<direct,NC>/f64",
+ * NC the columns of a full group, for an aligned d_input (one that is not is read in place); "" for NULL or a latched
+ * invalid topology.  num_rhs = 0 launches nothing.  Kernels only, asynchronous on `stream`.
+ * SIP_LQR_ERR_INVALID_ARGUMENT, before any HIP call: what sip_lqr_tree_residual rejects, num_rhs < 0, or num_rhs > 0
+ * with a NULL d_out_cols whose arena is not empty. */
+int sip_lqr_tree_residual_multi_columns(const sip_lqr_tree_plan *plan);
+const char *sip_lqr_tree_residual_multi_kernel_name(const sip_lqr_tree_plan *plan);
+int sip_lqr_tree_residual_multi(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_rhs_cols,
+                                const double *d_out_cols, int num_rhs, double *d_res_cols, double *d_norms,
+                                void *stream);
+
+/* sip_lqr_tree_refine for several right-hand sides: the contract of sip_lqr_tree_refine per column, the columns of
+ * d_rhs_cols and d_out_cols laid out as above.  `iterations` (1 .. 32) rounds of
+ *   the scaled residual of all columns (sip_lqr_tree_residual_multi's kernel), rho / s_{p,c} with one power of two
+ *             per problem AND column, never one shared by the columns of a problem;
+ *   one sip_lqr_tree_solve_multi on all num_rhs columns;
+ *   d_out_cols[c][p] += s_{p,c} * d[c][p], skipped in every column of a problem where d_status[p] != SIP_LQR_SUCCESS;
+ * then one more residual of all columns.  from_zero as for sip_lqr_tree_refine.
+ *   d_norms : (iterations + 1) * num_rhs * batch doubles; d_norms[(j * num_rhs + c) * batch + p] is max |rho| of
+ *             problem p in column c before round j + 1, the last row that of the result;
+ *   d_refine_workspace: sip_lqr_tree_refine_multi_workspace_bytes(plan, num_rhs) of device scratch =
+ *             2 * up(num_rhs * batch * sip_lqr_tree_rhs_len() * 8) + up(num_rhs * batch * 8) +
+ *             up(sip_lqr_tree_solve_multi_scratch_bytes(plan, num_rhs)), up() rounding up to a multiple of 256:
+ *             rho / s, then d, both [num_rhs][batch][rhs_len] (sip_lqr_tree_solve_multi's column arrays as they
+ *             stand), then s[c][p], then the solve's scratch; 0 for NULL, a latched invalid topology or num_rhs < 1.
+ * num_rhs = 0 launches nothing.  Kernels only, no allocation and no synchronisation, asynchronous on `stream`.
+ * SIP_LQR_ERR_INVALID_ARGUMENT, before any HIP call: what sip_lqr_tree_refine rejects, num_rhs < 0, or num_rhs > 0
+ * with a NULL d_out_cols whose arena is not empty. */
+size_t sip_lqr_tree_refine_multi_workspace_bytes(const sip_lqr_tree_plan *plan, int num_rhs);
+int sip_lqr_tree_refine_multi(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_work,
+                              const double *d_rhs_cols, double *d_out_cols, int num_rhs, int iterations, int from_zero,
+                              const int32_t *d_status, void *d_refine_workspace, double *d_norms, void *stream);
+
 /* Name of the kernel variant the plan dispatches to (static string). */
 const char *sip_lqr_kernel_name(const sip_lqr_plan *plan);
 

@@ -85,6 +85,12 @@ _SIGNATURES = {
     "sip_lqr_tree_residual": (ctypes.c_int, [_P] * 7),
     "sip_lqr_tree_refine_workspace_bytes": (ctypes.c_size_t, [_P]),
     "sip_lqr_tree_refine": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P]),
+    "sip_lqr_tree_residual_multi_columns": (ctypes.c_int, [_P]),
+    "sip_lqr_tree_residual_multi_kernel_name": (ctypes.c_char_p, [_P]),
+    "sip_lqr_tree_residual_multi": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
+    "sip_lqr_tree_refine_multi_workspace_bytes": (ctypes.c_size_t, [_P, ctypes.c_int]),
+    "sip_lqr_tree_refine_multi": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P,
+                                                 _P, _P]),
     "sip_lqr_tree_factor_fused": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "sip_lqr_tree_solve_fused": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "sip_lqr_tree_split_kernel_name": (ctypes.c_char_p, [_P]),

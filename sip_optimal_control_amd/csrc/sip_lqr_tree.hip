@@ -15,6 +15,7 @@
 #include "residual_launch.hpp"
 #include "table_packer.hpp"
 #include "tree_plan.hpp"
+#include "tree_residual_cols_launch.hpp"
 #include "tree_residual_launch.hpp"
 
 struct sip_lqr_tree_plan {
@@ -28,6 +29,7 @@ struct sip_lqr_tree_plan {
   void *d_steps = nullptr;
   sipamd::TreeScratch scratch; // of the fused kernels: padded gains at 0, then the spill
   sipamd::residual::TreeShape residual; // of the residual kernel: staged or in place, wavefronts, LDS
+  sipamd::residual::TreeColsDims residual_cols; // what the launch shape of its column form reads of the plan
   ~sip_lqr_tree_plan() {
     if (d_steps != nullptr)
       (void)hipFree(d_steps);
@@ -112,6 +114,8 @@ int sip_lqr_tree_plan_create(int64_t batch, int num_edges, int root,
   hipError_t e = g.upload(device);
   p->residual = sipamd::residual::tree_launch_shape(N, E, g.state_dims.data(), g.control_dims.data(), g.parents.data(),
                                                     g.children.data());
+  p->residual_cols = sipamd::residual::tree_cols_dims(N, E, g.state_dims.data(), g.control_dims.data(),
+                                                      g.parents.data(), g.children.data());
   // size class of the fused kernels; where one holds the tree: its schedule and its scratch
   if (e == hipSuccess)
     p->fused = sipamd::choose_tree_class(g);
@@ -403,6 +407,114 @@ int sip_lqr_tree_refine(const sip_lqr_tree_plan *plan, const double *d_input, co
     e = sipamd::residual::launch_tree_residual(plan->g.meta, plan->residual, a, dev.s);
   }
   return report(e, "sip_lqr_tree_refine");
+}
+
+} // extern "C"
+
+// ---- the same for several columns (tree_residual_cols.hpp) ----------------------------------------------------------
+namespace {
+// sip_lqr_tree_refine_multi's scratch: rho / s and d as [num_rhs][batch][rhs_len], s[c][p], then the solve's scratch.
+TreeRefineWorkspace tree_refine_multi_layout(const sip_lqr_tree_plan *p, int num_rhs) {
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t cols = (size_t)num_rhs;
+  const size_t vec = up(cols * (size_t)p->batch * (size_t)p->g.out_len * sizeof(double));
+  TreeRefineWorkspace w;
+  w.d = vec;
+  w.scale = 2 * vec;
+  w.solve = w.scale + up(cols * (size_t)p->batch * sizeof(double));
+  w.total = w.solve + up(sip_lqr_tree_solve_multi_scratch_bytes(p, num_rhs));
+  return w;
+}
+sipamd::residual::TreeColsShape full_group(const sip_lqr_tree_plan *p) {
+  return sipamd::residual::tree_cols_shape(p->residual_cols, true, sipamd::residual::kTreeColsMax);
+}
+bool valid_plan(const sip_lqr_tree_plan *p) { return p != nullptr && p->topology_status == SIP_LQR_SUCCESS; }
+} // namespace
+
+extern "C" {
+
+int sip_lqr_tree_residual_multi_columns(const sip_lqr_tree_plan *plan) {
+  return valid_plan(plan) ? full_group(plan).columns : 0;
+}
+
+const char *sip_lqr_tree_residual_multi_kernel_name(const sip_lqr_tree_plan *plan) {
+  if (!valid_plan(plan)) // (a latched topology: no launch, no kernel)
+    return "";
+  static const char *const names[2][4] = {
+      {"tree_residual_cols<direct,1>/f64", "tree_residual_cols<direct,2>/f64", "tree_residual_cols<direct,4>/f64",
+       "tree_residual_cols<direct,8>/f64"},
+      {"tree_residual_cols<staged,1>/f64", "tree_residual_cols<staged,2>/f64", "tree_residual_cols<staged,4>/f64",
+       "tree_residual_cols<staged,8>/f64"}};
+  const sipamd::residual::TreeColsShape sh = full_group(plan);
+  const int k = sh.columns >= 8 ? 3 : (sh.columns >= 4 ? 2 : (sh.columns >= 2 ? 1 : 0));
+  // (one column per launch: the single-column kernel, staged where that kernel is)
+  return names[(sh.columns > 1 ? sh.staged : plan->residual.staged) ? 1 : 0][k];
+}
+
+int sip_lqr_tree_residual_multi(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_rhs_cols,
+                                const double *d_out_cols, int num_rhs, double *d_res_cols, double *d_norms,
+                                void *stream) {
+  if (plan == nullptr || d_norms == nullptr || num_rhs < 0 || missing_input(plan, d_input) ||
+      (num_rhs > 0 && missing_output(plan, d_out_cols)) || plan->topology_status != SIP_LQR_SUCCESS)
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  if (num_rhs == 0)
+    return SIP_LQR_OK;
+  OnPlanDevice dev(plan, stream);
+  if (dev.rc != SIP_LQR_OK)
+    return dev.rc;
+  sipamd::residual::TreeColsArgs a{};
+  a.batch = (long)plan->batch, a.input = d_input, a.rhs_cols = d_rhs_cols, a.sol_cols = d_out_cols;
+  a.res = d_res_cols, a.norm = d_norms;
+  return report(sipamd::residual::launch_tree_residual_cols(plan->g.meta, plan->residual_cols, plan->residual, a,
+                                                            num_rhs, dev.s),
+                "sip_lqr_tree_residual_multi");
+}
+
+size_t sip_lqr_tree_refine_multi_workspace_bytes(const sip_lqr_tree_plan *plan, int num_rhs) {
+  return valid_plan(plan) && num_rhs >= 1 ? tree_refine_multi_layout(plan, num_rhs).total : 0;
+}
+
+int sip_lqr_tree_refine_multi(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_work,
+                              const double *d_rhs_cols, double *d_out_cols, int num_rhs, int iterations, int from_zero,
+                              const int32_t *d_status, void *d_refine_workspace, double *d_norms, void *stream) {
+  if (plan == nullptr || d_status == nullptr || d_work == nullptr || d_refine_workspace == nullptr ||
+      d_norms == nullptr || num_rhs < 0 || missing_input(plan, d_input) ||
+      (num_rhs > 0 && missing_output(plan, d_out_cols)) || iterations < 1 || iterations > 32 ||
+      (from_zero != 0 && from_zero != 1) || plan->topology_status != SIP_LQR_SUCCESS)
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  if (num_rhs == 0)
+    return SIP_LQR_OK;
+  OnPlanDevice dev(plan, stream);
+  if (dev.rc != SIP_LQR_OK)
+    return dev.rc;
+  const TreeRefineWorkspace f = tree_refine_multi_layout(plan, num_rhs);
+  char *w = (char *)d_refine_workspace;
+  double *rho = (double *)w, *d = (double *)(w + f.d), *scale = (double *)(w + f.scale);
+  const long B = (long)plan->batch, len = plan->g.out_len;
+  const size_t row = (size_t)num_rhs * B; // norms of one round
+  sipamd::residual::TreeColsArgs a{};
+  a.batch = B, a.input = d_input, a.rhs_cols = d_rhs_cols, a.sol_cols = d_out_cols;
+  auto residual = [&]() {
+    return sipamd::residual::launch_tree_residual_cols(plan->g.meta, plan->residual_cols, plan->residual, a, num_rhs,
+                                                       dev.s);
+  };
+  hipError_t e = from_zero ? sipamd::zero_async(d_out_cols, row * len * sizeof(double), dev.s) : hipSuccess;
+  for (int j = 0; j < iterations && e == hipSuccess; ++j) {
+    a.scaled = rho, a.scale = scale, a.norm = d_norms + (size_t)j * row;
+    e = residual();
+    if (e != hipSuccess)
+      break;
+    // (an empty output arena: rho and d have no entries, and the solve's check of them does not apply)
+    const int rc = sip_lqr_tree_solve_multi(plan, d_input, d_work, rho, d, num_rhs, d_status, w + f.solve, stream);
+    if (rc != SIP_LQR_OK)
+      return rc;
+    e = sipamd::residual::launch_update_cols(num_rhs, B, len, false, d, scale, d_status, d_out_cols, dev.s);
+  }
+  if (e == hipSuccess) { // the norms of the result
+    a.scaled = nullptr, a.scale = nullptr, a.norm = d_norms + (size_t)iterations * row;
+    e = residual();
+  }
+  return report(e, "sip_lqr_tree_refine_multi");
 }
 
 } // extern "C"

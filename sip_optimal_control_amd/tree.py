@@ -250,6 +250,66 @@ class BatchedTreeLQR:
                                              ctypes.c_void_p(s.cuda_stream)), "sip_lqr_tree_refine")
         return output, norms
 
+    @property
+    def residual_multi_kernel_name(self):
+        return self._lib.sip_lqr_tree_residual_multi_kernel_name(self._plan).decode()
+
+    @property
+    def residual_multi_columns(self):
+        """Columns one launch of residual_multi carries on this plan (sip_lqr_tree_residual_multi_columns)."""
+        return int(self._lib.sip_lqr_tree_residual_multi_columns(self._plan))
+
+    def _cols(self, t, name):
+        """num_rhs of a contiguous float64 [num_rhs, batch, rhs_len] column array on the plan's device."""
+        if t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous() or t.dim() != 3 \
+                or tuple(t.shape[1:]) != (self.batch, max(1, self.rhs_len)):
+            raise ValueError(f"{name}: expected contiguous torch.float64 "
+                             f"[num_rhs, {self.batch}, {max(1, self.rhs_len)}] on {self.device}")
+        return int(t.shape[0])
+
+    def residual_multi(self, out_cols, rhs_cols=None, want_vector=True):
+        """residual() for several iterates and right-hand sides against one `input` (sip_lqr_tree_residual_multi):
+        out_cols (num_rhs, batch, output_len) as solve_multi returns them; rhs_cols likewise (pack_rhs), or None: q, c, r
+        of `input` for every column.  Returns (res_cols [num_rhs, batch, rhs_len], or None with want_vector=False;
+        norms [num_rhs, batch]).  Column c is bit for bit residual(out_cols[c], rhs=rhs_cols[c])."""
+        num_rhs = self._cols(out_cols, "out_cols")
+        if rhs_cols is not None and self._cols(rhs_cols, "rhs_cols") != num_rhs:
+            raise ValueError("rhs_cols: as many columns as out_cols")
+        res = torch.empty(num_rhs, self.batch, max(1, self.rhs_len), dtype=torch.float64, device=self.device) \
+            if want_vector else None
+        norms = torch.empty(num_rhs, self.batch, dtype=torch.float64, device=self.device)
+        s = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_tree_residual_multi(
+            self._plan, ctypes.c_void_p(self.input.data_ptr()),
+            ctypes.c_void_p(rhs_cols.data_ptr() if rhs_cols is not None else None),
+            ctypes.c_void_p(out_cols.data_ptr()), num_rhs, ctypes.c_void_p(res.data_ptr() if want_vector else None),
+            ctypes.c_void_p(norms.data_ptr()), ctypes.c_void_p(s.cuda_stream)), "sip_lqr_tree_residual_multi")
+        return res, norms
+
+    def refine_multi(self, rhs_cols, iterations=2, out_cols=None):
+        """refine() for several right-hand sides around solve_multi(), against the factor state in `work`
+        (sip_lqr_tree_refine_multi): rhs_cols (num_rhs, batch, rhs_len) (pack_rhs); out_cols the starting iterates,
+        refined in place, or None: from zero (round 1 is then the plain solve_multi).  A problem whose status is not
+        SUCCESS keeps its iterate in every column.  Returns (out_cols, norms [iterations + 1, num_rhs, batch])."""
+        num_rhs = self._cols(rhs_cols, "rhs_cols")
+        from_zero = out_cols is None
+        if from_zero:
+            out_cols = torch.empty(num_rhs, self.batch, max(1, self.out_len), dtype=torch.float64, device=self.device)
+        if self._cols(out_cols, "out_cols") != num_rhs:
+            raise ValueError("out_cols: as many columns as rhs_cols")
+        norms = torch.empty(int(iterations) + 1, num_rhs, self.batch, dtype=torch.float64, device=self.device)
+        need = self._lib.sip_lqr_tree_refine_multi_workspace_bytes(self._plan, num_rhs)
+        if getattr(self, "_refine_multi_scratch", None) is None or self._refine_multi_scratch.numel() < need:
+            self._refine_multi_scratch = torch.empty(max(1, need), dtype=torch.uint8, device=self.device)
+        s = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_tree_refine_multi(
+            self._plan, ctypes.c_void_p(self.input.data_ptr()), ctypes.c_void_p(self.work.data_ptr()),
+            ctypes.c_void_p(rhs_cols.data_ptr()), ctypes.c_void_p(out_cols.data_ptr()), num_rhs, int(iterations),
+            1 if from_zero else 0, ctypes.c_void_p(self.status.data_ptr()),
+            ctypes.c_void_p(self._refine_multi_scratch.data_ptr()), ctypes.c_void_p(norms.data_ptr()),
+            ctypes.c_void_p(s.cuda_stream)), "sip_lqr_tree_refine_multi")
+        return out_cols, norms
+
     def unpack_solution(self, b=0, output=None):
         out = (self.output[b] if output is None else output[b]).cpu().numpy()
         x, y, u = [], [], []
