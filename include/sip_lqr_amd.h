@@ -396,6 +396,51 @@ int sip_lqr_refine_multi(const sip_lqr_plan *plan, const void *d_mats, const dou
                          void *d_workspace, void *d_col_workspace, void *d_refine_workspace,
                          const int32_t *d_status, double *d_norms, void *stream);
 
+/* Gradients of a scalar loss L(z) through the solve (no counterpart in the reference).  The chain entry points solve
+ * K z + b = 0 with z = (x, u, y), b = (q, r, c) and K symmetric (the formulas at sip_lqr_residual).  With g = dL/dz in
+ * the sol layout, the adjoint lambda solves K lambda + g = 0 -- the plan's own solve with g as the right-hand side --
+ * and dL/dvecs = lambda as it stands (slot q_i <-> x_i, slot c_i <-> y_i, slot r_i <-> u_i).  dL/dmats is a sum of
+ * outer products of lambda = (lx_i, ly_i, lu_i) and z = (x_i, y_i, u_i), block by block, in the plan's layout:
+ *   Q_i, FULL       1/2 (lx_i x_i^T + x_i lx_i^T), written to the whole square
+ *   Q_i, SYMMETRIC  packed entry (r, c): lx_r x_c + lx_c x_r for r > c, lx_r x_r for r = c
+ *   R_i             the same two rules with lu_i, u_i
+ *   delta_i         -ly_i o y_i
+ *   A_i             ly_{i+1} x_i^T + y_{i+1} lx_i^T
+ *   B_i             ly_{i+1} u_i^T + y_{i+1} lu_i^T
+ *   M_i             lx_i u_i^T + x_i lu_i^T
+ * Q and R are taken symmetric everywhere in this library: the FULL rule is the gradient over symmetric perturbations
+ * (dL = <G, dQ> for symmetric dQ), the SYMMETRIC rule the derivative with respect to the packed parameter, and the two
+ * agree: <G_full, dQ> = sum over the packed entries of g_rc dQ_rc.
+ *
+ * sip_lqr_vjp_mats is the kernel alone: d_grad_mats (batch * sip_lqr_mats_len() scalars) from d_sol (z) and d_adj
+ * (lambda).  Every plan has it (every dtype, shape, layout and opt-in: it reads nothing of `mats` and nothing of the
+ * workspace).  Products and sums are fp64 (fused multiply-adds), fp32 inputs are widened on load, the result is
+ * rounded once to the output scalar.
+ *   wide = 0: d_sol, d_adj and d_grad_mats are in the plan's dtype; wide = 1: all three are doubles, with the same
+ *             per-problem lengths (on an SIP_LQR_F64 plan the two are the same thing);
+ *   d_status: NULL, or the statuses the factor call wrote: a problem whose status != SIP_LQR_SUCCESS gets an all-zero
+ *             gradient, and its d_sol and d_adj (unspecified, possibly NaN) are not read.
+ * Every scalar of d_grad_mats is written exactly once; d_grad_mats need only be aligned to its scalar.  Kernels only,
+ * no allocation and no synchronisation, asynchronous on `stream`.  SIP_LQR_ERR_INVALID_ARGUMENT, before any HIP call:
+ * a NULL plan, d_sol, d_adj or d_grad_mats, or a `wide` that is neither 0 nor 1.
+ *
+ * sip_lqr_vjp is the whole backward pass in the plan's dtype, against the factor state of the last sip_lqr_factor() on
+ * d_workspace (the contract of sip_lqr_solve; d_gains is the buffer that call filled): sip_lqr_solve with d_grad_sol
+ * (g) as the right-hand side into d_grad_vecs (lambda = dL/dvecs), then the kernel above on d_sol and d_grad_vecs.
+ *   d_grad_mats: may be NULL: only lambda is wanted and the kernel is not launched;
+ *   d_status   : NULL, or the statuses the factor call wrote: a failed problem ends with all-zero grad_vecs and
+ *                all-zero grad_mats, whatever its solve left there.
+ * The k part of d_gains is unspecified afterwards (as for sip_lqr_refine); K is untouched.  The gains K | k are not
+ * differentiated: a loss that reads them gets no gradient from here.  sip_lqr_factor_solve alone does not leave the
+ * state this call needs on every plan: call sip_lqr_factor first, as for sip_lqr_solve.  No second derivative is
+ * offered.  SIP_LQR_ERR_INVALID_ARGUMENT, before any HIP call: a NULL plan, d_mats, d_sol, d_grad_sol, d_workspace or
+ * d_grad_vecs (d_gains when T > 0). */
+int sip_lqr_vjp_mats(const sip_lqr_plan *plan, const void *d_sol, const void *d_adj, int wide,
+                     const int32_t *d_status, void *d_grad_mats, void *stream);
+int sip_lqr_vjp(const sip_lqr_plan *plan, const void *d_mats, const void *d_sol, const void *d_grad_sol,
+                void *d_gains, void *d_workspace, const int32_t *d_status, void *d_grad_vecs, void *d_grad_mats,
+                void *stream);
+
 /* ------------------------------------------------------------------------
  * General trees / per-node dimensions (the full Topology + Dimensions model
  * of lqr.hpp:5-64): the path behind the drop-in C++ `LQR` adapter

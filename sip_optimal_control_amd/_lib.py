@@ -60,6 +60,8 @@ _SIGNATURES = {
     "sip_lqr_refine_multi_workspace_bytes": (ctypes.c_size_t, [_P, ctypes.c_int]),
     "sip_lqr_refine_multi": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P,
                                             _P, _P, _P]),
+    "sip_lqr_vjp_mats": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, _P, _P, _P]),
+    "sip_lqr_vjp": (ctypes.c_int, [_P] * 10),
     "sip_lqr_compile_topology": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_P] * 9),
     "sip_lqr_tree_plan_create": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P,
                                                 ctypes.c_int, _PP]),

@@ -74,6 +74,9 @@ class BatchedChainLQR:
         ws_elems = -(-self._lib.sip_lqr_workspace_bytes(handle) // esize)
         self.workspace = torch.empty(ws_elems, dtype=dtype, device=self.device)
         self.status = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
+        # bumped by every factor* call: what a saved backward pass compares to know whether the factor state in the
+        # workspace is still its own (autograd.chain_lqr_solve)
+        self.factor_generation = 0
 
     @property
     def kernel_name(self):
@@ -119,6 +122,7 @@ class BatchedChainLQR:
             gains = self.empty_gains()
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
+        self.factor_generation += 1
         _check(self._lib.sip_lqr_factor_solve(
             self._plan, self._ptr(mats, self.batch, s.mats_len, "mats"),
             self._ptr(vecs, self.batch, s.vecs_len, "vecs"),
@@ -159,6 +163,7 @@ class BatchedChainLQR:
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
         assert ab.dtype == torch.float64 and ab.stride(-1) == 1 and ab.shape[-1] >= s.n * (s.n + s.m)
+        self.factor_generation += 1
         _check(self._lib.sip_lqr_factor_solve_split(
             self._plan, ctypes.c_void_p(qmr.data_ptr()), ctypes.c_void_p(ab.data_ptr()),
             ctypes.c_int64(ab.stride(0)), ctypes.c_int64(ab.stride(1) if ab.dim() > 2 else 0),
@@ -178,6 +183,7 @@ class BatchedChainLQR:
             gains = self.empty_gains()
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
+        self.factor_generation += 1
         _check(self._lib.sip_lqr_factor(
             self._plan, self._ptr(mats, self.batch, s.mats_len, "mats"),
             self._ptr(gains, self.batch, s.gains_len, "gains"),
@@ -348,6 +354,52 @@ class BatchedChainLQR:
             ctypes.c_void_p(self.status.data_ptr() if use_status else None), ctypes.c_void_p(norms.data_ptr()),
             ctypes.c_void_p(stream.cuda_stream)), "sip_lqr_refine_multi")
         return sol_cols, norms
+
+    def vjp_mats(self, sol, adj, use_status=True, grad_mats=None, stream=None):
+        """dL/dmats [batch, mats_len] in the plan's layout from the solution and the adjoint (sip_lqr_vjp_mats): sol and
+        adj both in the plan's dtype or both float64, and the gradient in that dtype.  Problems whose factor status is
+        not SUCCESS get zeros (use_status=False: nothing is masked)."""
+        s = self.shape
+        wide = self._wide(sol, adj)
+        if grad_mats is None:
+            grad_mats = torch.empty(self.batch, s.mats_len, dtype=sol.dtype, device=self.device)
+        elif grad_mats.dtype != sol.dtype or grad_mats.device != self.device or not grad_mats.is_contiguous() \
+                or grad_mats.numel() != self.batch * s.mats_len:
+            raise ValueError(f"grad_mats: expected contiguous {sol.dtype} [{self.batch}, {s.mats_len}] on {self.device}")
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_vjp_mats(
+            self._plan, ctypes.c_void_p(sol.data_ptr()), ctypes.c_void_p(adj.data_ptr()), wide,
+            ctypes.c_void_p(self.status.data_ptr() if use_status else None), ctypes.c_void_p(grad_mats.data_ptr()),
+            ctypes.c_void_p(stream.cuda_stream)), "sip_lqr_vjp_mats")
+        return grad_mats
+
+    def vjp(self, mats, sol, grad_sol, gains, want_mats=True, use_status=True, refine_iterations=0, stream=None):
+        """The backward pass of the solve against the last factor(): (grad_mats or None, grad_vecs) of a loss whose
+        gradient with respect to `sol` is grad_sol.  grad_vecs is the adjoint lambda (K lambda + grad_sol = 0), grad_mats
+        the outer products of include/sip_lqr_amd.h in the plan's layout; the gains are not differentiated.
+        refine_iterations = 0: one sip_lqr_vjp call, everything in the plan's dtype.  refine_iterations > 0: lambda
+        from refine() on the float64 grad_sol, the kernel on float64 sol and lambda, float64 gradients (the accurate
+        path of fp32 plans).  Problems whose factor status is not SUCCESS get zeros (use_status=False: whatever their
+        solve leaves)."""
+        s = self.shape
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        if refine_iterations > 0:
+            grad_vecs, _ = self.refine(mats, grad_sol.double().contiguous(), gains, iterations=refine_iterations,
+                                       use_status=use_status, stream=stream)
+            grad_mats = self.vjp_mats(sol.double().contiguous(), grad_vecs, use_status=use_status, stream=stream) \
+                if want_mats else None
+            return grad_mats, grad_vecs
+        grad_vecs = self.empty_sol()
+        grad_mats = torch.empty(self.batch, s.mats_len, dtype=self.dtype, device=self.device) if want_mats else None
+        _check(self._lib.sip_lqr_vjp(
+            self._plan, self._ptr(mats, self.batch, s.mats_len, "mats"), self._ptr(sol, self.batch, s.vecs_len, "sol"),
+            self._ptr(grad_sol, self.batch, s.vecs_len, "grad_sol"), self._ptr(gains, self.batch, s.gains_len, "gains"),
+            ctypes.c_void_p(self.workspace.data_ptr()), ctypes.c_void_p(self.status.data_ptr() if use_status else None),
+            ctypes.c_void_p(grad_vecs.data_ptr()), ctypes.c_void_p(grad_mats.data_ptr() if want_mats else None),
+            ctypes.c_void_p(stream.cuda_stream)), "sip_lqr_vjp")
+        return grad_mats, grad_vecs
 
     def close(self):
         if getattr(self, "_plan", None):

@@ -21,6 +21,7 @@
 #include "qw16_table.hpp"
 #include "residual_launch.hpp"
 #include "stream_fill.hpp"
+#include "vjp_launch.hpp"
 
 using sipamd::KernelEntry;
 
@@ -899,6 +900,60 @@ int sip_lqr_refine_multi(const sip_lqr_plan *plan, const void *d_mats, const dou
     e = sipamd::residual::launch_residual_cols(a, num_rhs, s);
   }
   return report(e, "sip_lqr_refine_multi");
+}
+
+} // extern "C"
+
+// ---- gradients of the solve: one adjoint solve and the outer-product kernel (chain_vjp.hpp) --------------------------
+namespace {
+sipamd::vjp::Args vjp_args(const sip_lqr_plan *p, const void *sol, const void *adj, bool wide, const int32_t *status,
+                           void *grad) {
+  sipamd::vjp::Args a{};
+  a.batch = (long)p->batch, a.T = p->T, a.n = p->n, a.m = p->m;
+  a.f32 = p->dtype == SIP_LQR_F32 && !wide;
+  a.symmetric = p->layout == SIP_LQR_LAYOUT_SYMMETRIC;
+  a.sol = sol, a.adj = adj, a.status = status, a.grad = grad;
+  return a;
+}
+} // namespace
+
+extern "C" {
+
+int sip_lqr_vjp_mats(const sip_lqr_plan *plan, const void *d_sol, const void *d_adj, int wide,
+                     const int32_t *d_status, void *d_grad_mats, void *stream) {
+  if (plan == nullptr || !d_sol || !d_adj || !d_grad_mats || (wide != 0 && wide != 1))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  OnPlanDevice on_device(plan, "sip_lqr_vjp_mats");
+  if (on_device.rc != SIP_LQR_OK)
+    return on_device.rc;
+  return report(sipamd::vjp::launch_vjp(vjp_args(plan, d_sol, d_adj, wide == 1, d_status, d_grad_mats),
+                                        (hipStream_t)stream),
+                "sip_lqr_vjp_mats");
+}
+
+int sip_lqr_vjp(const sip_lqr_plan *plan, const void *d_mats, const void *d_sol, const void *d_grad_sol,
+                void *d_gains, void *d_workspace, const int32_t *d_status, void *d_grad_vecs, void *d_grad_mats,
+                void *stream) {
+  if (plan == nullptr || !d_mats || !d_sol || !d_grad_sol || !d_workspace || !d_grad_vecs ||
+      (plan->T > 0 && !d_gains))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  // lambda: K lambda + g = 0 is the plan's solve with g as the right-hand side, and dL/dvecs as it stands
+  const int rc = sip_lqr_solve(plan, d_mats, d_grad_sol, d_grad_vecs, d_gains, d_workspace, stream);
+  if (rc != SIP_LQR_OK)
+    return rc;
+  if (d_status == nullptr && d_grad_mats == nullptr)
+    return SIP_LQR_OK;
+  OnPlanDevice on_device(plan, "sip_lqr_vjp");
+  if (on_device.rc != SIP_LQR_OK)
+    return on_device.rc;
+  hipError_t e = hipSuccess;
+  if (d_status != nullptr) // whatever the solve left for a failed problem
+    e = sipamd::vjp::launch_mask((long)plan->batch, lens(plan).vecs, plan->dtype == SIP_LQR_F32, d_status,
+                                 d_grad_vecs, (hipStream_t)stream);
+  if (e == hipSuccess && d_grad_mats != nullptr)
+    e = sipamd::vjp::launch_vjp(vjp_args(plan, d_sol, d_grad_vecs, false, d_status, d_grad_mats),
+                                (hipStream_t)stream);
+  return report(e, "sip_lqr_vjp");
 }
 
 } // extern "C"
