@@ -683,6 +683,62 @@ int sip_lqr_tree_refine_multi(const sip_lqr_tree_plan *plan, const double *d_inp
                               const double *d_rhs_cols, double *d_out_cols, int num_rhs, int iterations, int from_zero,
                               const int32_t *d_status, void *d_refine_workspace, double *d_norms, void *stream);
 
+/* Gradients of a scalar loss L(z) through the tree solve (no counterpart in the reference; the tree twin of
+ * sip_lqr_vjp).  The tree entry points solve K z + b = 0 with z = (x_i, y_i per node; u_e per edge),
+ * b = (q_i, c_i; r_e) and K symmetric (its rows are the rho_* formulas at sip_lqr_tree_residual).  With g = dL/dz in the
+ * output arena's layout, the adjoint lambda solves K lambda + g = 0 -- sip_lqr_tree_solve_multi with one column and g
+ * as the right-hand side -- and dL/db = lambda as it stands (slot q_i <-> x_i, slot c_i <-> y_i, slot r_e <-> u_e);
+ * dL/dK = lambda z^T.  The gradient with respect to the input arena is an array in the input arena's own layout,
+ * sip_lqr_tree_input_len() doubles per problem (node blocks Q | q | c | delta, edge blocks A | B | M | R | r, matrices
+ * column-major), from lambda = (lx_i, ly_i; lu_e) and z; for node i, and edge e with parent p and child c:
+ *   Q_i (n x n)    (r, col)  1/2 (lx_i[r] x_i[col] + x_i[r] lx_i[col]), written to the whole square
+ *   q_i, c_i       j         lx_i[j], ly_i[j]
+ *   delta_i        j         -ly_i[j] y_i[j]
+ *   A_e (nc x np)  (r, col)  ly_c[r] x_p[col] + y_c[r] lx_p[col]
+ *   B_e (nc x m)   (r, col)  ly_c[r] u_e[col] + y_c[r] lu_e[col]
+ *   M_e (np x m)   (r, col)  lx_p[r] u_e[col] + x_p[r] lu_e[col]
+ *   R_e (m x m)    (r, col)  1/2 (lu_e[r] u_e[col] + u_e[r] lu_e[col])
+ *   r_e            j         lu_e[j]
+ * Q and R follow the chain's FULL rule: the gradient over symmetric perturbations, dL = <G, dQ> for symmetric dQ.
+ * The gains K | k and the other fields of the work arena are not differentiated: a loss that reads them gets no
+ * gradient from here.  Gradients through sip_kkt_* are not offered.  No second derivative is offered.
+ *
+ * sip_lqr_tree_vjp_input is the kernel alone: d_grad_input (batch * sip_lqr_tree_input_len() doubles) from d_output
+ * (z) and d_adj (lambda), both batch * sip_lqr_tree_output_len() doubles.  Every valid plan has it, on either engine,
+ * dimensions of 0, a single node and no edges included: it reads nothing of the input or work arenas, only a table the
+ * plan built when it was created (8 bytes per input-arena scalar on the device, freed with the plan).  An entry is
+ * fma(lambda[ia], z[ib], z[ia] * lambda[ib]) in fp64 times 1, 1/2 or -1/2, or a copy of lambda.
+ *   d_status: NULL, or the statuses the factor call wrote: a problem whose status != SIP_LQR_SUCCESS gets an all-zero
+ *             gradient, and its d_output and d_adj (unspecified, possibly NaN) are not read.
+ * Every scalar of d_grad_input is written exactly once and nothing else is; d_grad_input need only be aligned to 8
+ * bytes; no atomics: two launches give the same bits.  An empty input arena launches nothing.
+ * sip_lqr_tree_vjp_kernel_name(): "tree_vjp<staged>/f64" (z and lambda of a problem go through LDS) or
+ * "tree_vjp<direct>/f64" (16 * sip_lqr_tree_output_len() bytes exceed 64 KiB: read in place), decided per plan; "" for
+ * NULL or a latched invalid topology.  Kernels only, no allocation, copy or synchronisation, asynchronous on `stream`.
+ * SIP_LQR_ERR_INVALID_ARGUMENT, before any HIP call: a NULL plan, a latched invalid topology, a NULL d_output, d_adj
+ * or d_grad_input whose arena is not empty.
+ *
+ * sip_lqr_tree_vjp is the whole backward pass against the factor state in d_work (left by sip_lqr_tree_factor(),
+ * sip_lqr_tree_factor_fused() or sip_lqr_tree_factor_solve_workspace(); only read), on the fused size-class kernels
+ * and on the general engine alike: sip_lqr_tree_solve_multi with one column and d_grad_output (g) as the right-hand
+ * side into d_adj (lambda = dL/d(q, c, r)); d_adj of every problem whose status != SIP_LQR_SUCCESS zeroed (the solve
+ * leaves those untouched); then the kernel above on d_output and d_adj.
+ *   d_status    : required: the statuses the factor call wrote; a failed problem ends with all-zero d_adj and
+ *                 all-zero d_grad_input;
+ *   d_grad_input: may be NULL: only lambda is wanted, the kernel is not launched and d_output is not needed;
+ *   d_scratch   : sip_lqr_tree_vjp_scratch_bytes(plan) = sip_lqr_tree_solve_multi_scratch_bytes(plan, 1) of device
+ *                 scratch.
+ * Kernels only, no allocation, copy or synchronisation, asynchronous on `stream`.  SIP_LQR_ERR_INVALID_ARGUMENT,
+ * before any HIP call: a NULL plan, a latched invalid topology, a NULL d_status, d_work or d_scratch, a NULL d_input,
+ * d_grad_output or d_adj whose arena is not empty, a NULL d_output with d_grad_input given. */
+const char *sip_lqr_tree_vjp_kernel_name(const sip_lqr_tree_plan *plan);
+int sip_lqr_tree_vjp_input(const sip_lqr_tree_plan *plan, const double *d_output, const double *d_adj,
+                           const int32_t *d_status, double *d_grad_input, void *stream);
+size_t sip_lqr_tree_vjp_scratch_bytes(const sip_lqr_tree_plan *plan);
+int sip_lqr_tree_vjp(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_work,
+                     const double *d_output, const double *d_grad_output, const int32_t *d_status, double *d_adj,
+                     double *d_grad_input, void *d_scratch, void *stream);
+
 /* Name of the kernel variant the plan dispatches to (static string). */
 const char *sip_lqr_kernel_name(const sip_lqr_plan *plan);
 

@@ -1,4 +1,5 @@
-"""The chain solve as a differentiable torch function: sol = chain_lqr_solve(solver, mats, vecs).
+"""The solves as differentiable torch functions: sol = chain_lqr_solve(solver, mats, vecs) and
+output = tree_lqr_solve(solver, input).  The chain first; the tree twin follows the same scheme (below).
 
 Forward is solver.factor(mats) + solver.solve(...); backward is one adjoint solve against that factorisation and the
 outer-product kernel (BatchedChainLQR.vjp, sip_lqr_vjp), all on the device.  The factor state lives in the solver's
@@ -40,3 +41,44 @@ def chain_lqr_solve(solver, mats, vecs, return_status=False):
     whose status is not SUCCESS has an unspecified sol and gets zero gradients."""
     sol, status = _ChainLQRSolve.apply(solver, mats, vecs)
     return (sol, status) if return_status else sol
+
+
+class _TreeLQRSolve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, solver, input):
+        solver.input.copy_(input.detach().reshape(solver.input.shape))
+        solver.factor_fused()
+        solver.solve_fused()
+        ctx.solver = solver
+        ctx.generation = solver.factor_generation
+        output, status = solver.output.clone(), solver.status.clone()  # the solver's own buffers are rewritten later
+        ctx.save_for_backward(input.detach().clone(), output)
+        ctx.mark_non_differentiable(status)
+        return output, status
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output, _grad_status):
+        solver = ctx.solver
+        input, output = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None
+        if solver.factor_generation != ctx.generation:  # someone packed or factored since: neither arena is ours
+            solver.input.copy_(input.reshape(solver.input.shape))
+            solver.factor_fused()
+            ctx.generation = solver.factor_generation
+        grad_input, _ = solver.vjp(grad_output.contiguous(), output=output, want_input=True)
+        return None, grad_input.reshape(input.shape)
+
+
+def tree_lqr_solve(solver, input, return_status=False):
+    """output [batch, output_len] of `solver` (a BatchedTreeLQR) on `input` [batch, in_len] (the input arena: node
+    blocks Q | q | c | delta, edge blocks A | B | M | R | r, as pack() writes them), differentiable with respect to it.
+    Forward copies `input` into solver.input and runs factor_fused() + solve_fused(); backward is one solver.vjp
+    (sip_lqr_tree_vjp).  Forward remembers solver.factor_generation, which pack() and every factor* call bump: a
+    backward pass that finds another value copies the saved input back and factors again first, so stale factor state
+    or a foreign input arena is never used.  return_status=True: (output, status), status the int32 factor statuses of
+    this call (not differentiable); a problem whose status is not SUCCESS has an unspecified output and gets zero
+    gradients.  The gains are not differentiated, and there is no second derivative."""
+    output, status = _TreeLQRSolve.apply(solver, input)
+    return (output, status) if return_status else output

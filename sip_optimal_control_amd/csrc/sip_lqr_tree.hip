@@ -17,6 +17,8 @@
 #include "tree_plan.hpp"
 #include "tree_residual_cols_launch.hpp"
 #include "tree_residual_launch.hpp"
+#include "tree_vjp_launch.hpp"
+#include "vjp_launch.hpp"
 
 struct sip_lqr_tree_plan {
   int64_t batch = 0;
@@ -30,9 +32,12 @@ struct sip_lqr_tree_plan {
   sipamd::TreeScratch scratch; // of the fused kernels: padded gains at 0, then the spill
   sipamd::residual::TreeShape residual; // of the residual kernel: staged or in place, wavefronts, LDS
   sipamd::residual::TreeColsDims residual_cols; // what the launch shape of its column form reads of the plan
+  void *d_vjp_table = nullptr; // of the gradient kernel (tree_vjp_table.hpp): one word per input-arena scalar
   ~sip_lqr_tree_plan() {
     if (d_steps != nullptr)
       (void)hipFree(d_steps);
+    if (d_vjp_table != nullptr)
+      (void)hipFree(d_vjp_table);
   }
 };
 
@@ -48,6 +53,14 @@ hipError_t upload_schedule(sip_lqr_tree_plan *p) {
   steps.push(h.backward, &p->sched.backward), steps.push(h.forward, &p->sched.forward);
   sipamd::DeviceGuard on_device(p->device);
   return on_device.err != hipSuccess ? on_device.err : steps.upload(&p->d_steps);
+}
+
+// The table of the gradient kernel on the plan's device.
+hipError_t upload_vjp_table(sip_lqr_tree_plan *p) {
+  sipamd::TablePacker<sipamd::tree_vjp::Word> words;
+  words.push(sipamd::tree_vjp::build_table(p->g));
+  sipamd::DeviceGuard on_device(p->device);
+  return on_device.err != hipSuccess ? on_device.err : words.upload(&p->d_vjp_table);
 }
 
 // The preamble of a compute entry point: the plan's device is the current one while this lives, whatever the
@@ -112,6 +125,8 @@ int sip_lqr_tree_plan_create(int64_t batch, int num_edges, int root,
   // layout, upload
   g.layout_tree_native();
   hipError_t e = g.upload(device);
+  if (e == hipSuccess)
+    e = upload_vjp_table(p);
   p->residual = sipamd::residual::tree_launch_shape(N, E, g.state_dims.data(), g.control_dims.data(), g.parents.data(),
                                                     g.children.data());
   p->residual_cols = sipamd::residual::tree_cols_dims(N, E, g.state_dims.data(), g.control_dims.data(),
@@ -515,6 +530,67 @@ int sip_lqr_tree_refine_multi(const sip_lqr_tree_plan *plan, const double *d_inp
     e = residual();
   }
   return report(e, "sip_lqr_tree_refine_multi");
+}
+
+} // extern "C"
+
+// ---- gradients of the solve: one adjoint solve and the outer-product kernel (tree_vjp.hpp) --------------------------
+namespace {
+sipamd::tree_vjp::Args tree_vjp_args(const sip_lqr_tree_plan *p, const double *sol, const double *adj,
+                                     const int32_t *status, double *grad) {
+  sipamd::tree_vjp::Args a{};
+  a.batch = (long)p->batch, a.in_len = p->g.in0_len, a.out_len = p->g.out_len;
+  a.table = (const sipamd::tree_vjp::Word *)p->d_vjp_table;
+  a.sol = sol, a.adj = adj, a.status = status, a.grad = grad;
+  return a;
+}
+} // namespace
+
+extern "C" {
+
+const char *sip_lqr_tree_vjp_kernel_name(const sip_lqr_tree_plan *plan) {
+  if (!valid_plan(plan)) // (a latched topology: no table, no kernel)
+    return "";
+  return sipamd::tree_vjp::kernel_name(
+      sipamd::tree_vjp::launch_shape(plan->g.in0_len, plan->g.out_len, (long)plan->batch));
+}
+
+int sip_lqr_tree_vjp_input(const sip_lqr_tree_plan *plan, const double *d_output, const double *d_adj,
+                           const int32_t *d_status, double *d_grad_input, void *stream) {
+  if (!valid_plan(plan) || missing_output(plan, d_output) || missing_output(plan, d_adj) ||
+      missing_input(plan, d_grad_input))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  OnPlanDevice dev(plan, stream);
+  if (dev.rc != SIP_LQR_OK)
+    return dev.rc;
+  return report(sipamd::tree_vjp::launch_tree_vjp(tree_vjp_args(plan, d_output, d_adj, d_status, d_grad_input), dev.s),
+                "sip_lqr_tree_vjp_input");
+}
+
+size_t sip_lqr_tree_vjp_scratch_bytes(const sip_lqr_tree_plan *plan) {
+  return sip_lqr_tree_solve_multi_scratch_bytes(plan, 1);
+}
+
+int sip_lqr_tree_vjp(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_work,
+                     const double *d_output, const double *d_grad_output, const int32_t *d_status, double *d_adj,
+                     double *d_grad_input, void *d_scratch, void *stream) {
+  if (!valid_plan(plan) || d_status == nullptr || d_work == nullptr || d_scratch == nullptr ||
+      missing_input(plan, d_input) || missing_output(plan, d_grad_output) || missing_output(plan, d_adj) ||
+      (d_grad_input != nullptr && missing_output(plan, d_output)))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  // lambda: K lambda + g = 0 is the plan's one-column solve with g as the right-hand side, and dL/d(q, c, r) as it stands
+  const int rc = sip_lqr_tree_solve_multi(plan, d_input, d_work, d_grad_output, d_adj, 1, d_status, d_scratch, stream);
+  if (rc != SIP_LQR_OK)
+    return rc;
+  OnPlanDevice dev(plan, stream);
+  if (dev.rc != SIP_LQR_OK)
+    return dev.rc;
+  hipError_t e = hipSuccess;
+  if (plan->g.out_len > 0) // the solve leaves a failed problem's column untouched
+    e = sipamd::vjp::launch_mask((long)plan->batch, plan->g.out_len, false, d_status, d_adj, dev.s);
+  if (e == hipSuccess && d_grad_input != nullptr)
+    e = sipamd::tree_vjp::launch_tree_vjp(tree_vjp_args(plan, d_output, d_adj, d_status, d_grad_input), dev.s);
+  return report(e, "sip_lqr_tree_vjp");
 }
 
 } // extern "C"

@@ -58,6 +58,8 @@ class BatchedTreeLQR:
         self.work = torch.zeros(self.batch, max(1, self.ws_len), dtype=f64, device=self.device)
         self.output = torch.zeros(self.batch, max(1, self.out_len), dtype=f64, device=self.device)
         self.status = torch.full((self.batch,), -1, dtype=torch.int32, device=self.device)
+        # bumped by pack() and by every factor* call: what autograd.tree_lqr_solve remembers of the factor state
+        self.factor_generation = 0
 
     def offset(self, arena, kind, index):
         off = self._lib.sip_lqr_tree_offset(self._plan, arena, kind, index)
@@ -82,8 +84,10 @@ class BatchedTreeLQR:
                     host[b, o:o + a.size] = a
                     o += a.size
         self.input.copy_(torch.from_numpy(host))
+        self.factor_generation += 1
 
     def factor(self):
+        self.factor_generation += 1
         s = torch.cuda.current_stream(self.device)
         _check(self._lib.sip_lqr_tree_factor(self._plan, ctypes.c_void_p(self.input.data_ptr()),
                                              ctypes.c_void_p(self.work.data_ptr()),
@@ -99,6 +103,7 @@ class BatchedTreeLQR:
         """factor_with_status() + solve() as one fused sweep (size-class kernel of csrc/tree_qw16.hpp
         where the tree fits one, the general engine otherwise): output, status, K and k of `work`;
         workspace=True: every LQR::Workspace field of `work` (sip_lqr_tree_factor_solve_workspace)."""
+        self.factor_generation += 1
         s = torch.cuda.current_stream(self.device)
         entry = self._lib.sip_lqr_tree_factor_solve_workspace if workspace else self._lib.sip_lqr_tree_factor_solve
         scratch = self._fused_scratch()
@@ -123,6 +128,7 @@ class BatchedTreeLQR:
     def factor_fused(self):
         """factor_with_status() alone on the size-class kernel (sip_lqr_tree_factor_fused): the factor state of
         sip_lqr_tree_factor in `work`, statuses; q, r, c are not read and `output` is not written."""
+        self.factor_generation += 1
         s = torch.cuda.current_stream(self.device)
         _check(self._lib.sip_lqr_tree_factor_fused(self._plan, ctypes.c_void_p(self.input.data_ptr()),
                                                    ctypes.c_void_p(self.work.data_ptr()),
@@ -309,6 +315,63 @@ class BatchedTreeLQR:
             ctypes.c_void_p(self._refine_multi_scratch.data_ptr()), ctypes.c_void_p(norms.data_ptr()),
             ctypes.c_void_p(s.cuda_stream)), "sip_lqr_tree_refine_multi")
         return out_cols, norms
+
+    @property
+    def vjp_kernel_name(self):
+        return self._lib.sip_lqr_tree_vjp_kernel_name(self._plan).decode()
+
+    def _arena(self, t, length, name):
+        if t.dtype != torch.float64 or t.device != self.device or not t.is_contiguous() \
+                or t.numel() != self.batch * max(1, length):
+            raise ValueError(f"{name}: expected contiguous torch.float64 [{self.batch}, {max(1, length)}] on {self.device}")
+        return ctypes.c_void_p(t.data_ptr())
+
+    def vjp_input(self, output, adj, use_status=True, grad_input=None):
+        """The gradient kernel alone (sip_lqr_tree_vjp_input): grad_input [batch, in_len] in the input arena's layout
+        (written to `grad_input` when given) from output (z) and adj (lambda), both [batch, output_len]; use_status:
+        problems whose status != 0 get zeros."""
+        grad = grad_input if grad_input is not None else \
+            torch.empty(self.batch, max(1, self.in_len), dtype=torch.float64, device=self.device)
+        self._arena(grad, self.in_len, "grad_input")
+        s = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_tree_vjp_input(self._plan, self._arena(output, self.out_len, "output"),
+                                                self._arena(adj, self.out_len, "adj"),
+                                                ctypes.c_void_p(self.status.data_ptr() if use_status else None),
+                                                ctypes.c_void_p(grad.data_ptr()), ctypes.c_void_p(s.cuda_stream)),
+               "sip_lqr_tree_vjp_input")
+        return grad
+
+    def vjp(self, grad_output, output=None, want_input=True, refine_iterations=0):
+        """The backward pass of the solve for a loss with dL/d(output) = grad_output [batch, output_len], against the
+        factor state in `work` (left by factor(), factor_fused() or factor_solve(workspace=True)) (sip_lqr_tree_vjp):
+        one adjoint solve, K adj + grad_output = 0, then the outer-product kernel on `output` (default: self.output)
+        and adj.  Returns (grad_input [batch, in_len] in the input arena's layout, or None with want_input=False;
+        adj [batch, output_len] = dL/d(q, c, r) in the layout of a right-hand side).  refine_iterations > 0: adj comes
+        from that many rounds of refine() on grad_output instead of the plain solve.  Problems whose status != 0 get
+        zeros in both.  The gains are not differentiated."""
+        output = self.output if output is None else output
+        g = self._arena(grad_output, self.out_len, "grad_output")
+        if want_input:
+            self._arena(output, self.out_len, "output")
+        if int(refine_iterations) > 0:
+            adj = torch.zeros(self.batch, max(1, self.out_len), dtype=torch.float64, device=self.device)
+            self.refine(iterations=int(refine_iterations), rhs=grad_output, output=adj)
+            adj.masked_fill_((self.status != 0).unsqueeze(1), 0.0)
+            return (self.vjp_input(output, adj) if want_input else None), adj
+        adj = torch.empty(self.batch, max(1, self.out_len), dtype=torch.float64, device=self.device)
+        grad = torch.empty(self.batch, max(1, self.in_len), dtype=torch.float64, device=self.device) \
+            if want_input else None
+        need = self._lib.sip_lqr_tree_vjp_scratch_bytes(self._plan)
+        if getattr(self, "_multi_scratch", None) is None or self._multi_scratch.numel() < need:
+            self._multi_scratch = torch.empty(max(1, need), dtype=torch.uint8, device=self.device)
+        s = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_tree_vjp(self._plan, ctypes.c_void_p(self.input.data_ptr()),
+                                          ctypes.c_void_p(self.work.data_ptr()), ctypes.c_void_p(output.data_ptr()), g,
+                                          ctypes.c_void_p(self.status.data_ptr()), ctypes.c_void_p(adj.data_ptr()),
+                                          ctypes.c_void_p(grad.data_ptr() if want_input else None),
+                                          ctypes.c_void_p(self._multi_scratch.data_ptr()),
+                                          ctypes.c_void_p(s.cuda_stream)), "sip_lqr_tree_vjp")
+        return grad, adj
 
     def unpack_solution(self, b=0, output=None):
         out = (self.output[b] if output is None else output[b]).cpu().numpy()
