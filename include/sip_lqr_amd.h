@@ -441,6 +441,48 @@ int sip_lqr_vjp(const sip_lqr_plan *plan, const void *d_mats, const void *d_sol,
                 void *d_gains, void *d_workspace, const int32_t *d_status, void *d_grad_vecs, void *d_grad_mats,
                 void *stream);
 
+/* The gradient for several right-hand sides against one d_mats: the caller solved K z_c + b_c = 0 for num_rhs columns
+ * (sip_lqr_solve_multi) and the loss reads all the z_c, so dL/dmats = sum over c of G(lambda_c, z_c), G the outer
+ * products above.  The columns are laid out as for sip_lqr_solve_multi: column c of d_sol_cols, d_adj_cols,
+ * d_grad_sol_cols and d_grad_vecs_cols is a whole-batch array at c * batch * sip_lqr_vecs_len() scalars.  d_grad_mats
+ * is ONE array of batch * sip_lqr_mats_len() scalars: the sum over the columns.
+ *
+ * sip_lqr_vjp_mats_multi is the kernel alone (`wide`, d_status and "every plan has it" as for sip_lqr_vjp_mats).  One
+ * launch carries sip_lqr_vjp_multi_columns() columns (8, or fewer where 8 columns of one stage of z and lambda do not
+ * fit 64 KiB of LDS; 0 for a NULL plan): it reads every column once and writes d_grad_mats once.  An entry is summed
+ * in fp64 in ascending column order -- column 0 by the expression of sip_lqr_vjp_mats, every further column by two
+ * fused multiply-adds onto the running sum -- and rounded once to the output scalar, so num_rhs = 1 gives the bits of
+ * sip_lqr_vjp_mats.  More columns go in groups of that many, one launch per group.  The accumulate rule: the first
+ * group never reads d_grad_mats; every later group reads the scalar the groups before left there, undoes the factor
+ * 1, 1/2 or -1/2 exactly, continues the same chain of fused multiply-adds from it and stores again.  With double
+ * output the result therefore does not depend on the grouping (barring underflow); with float output every group
+ * boundary costs one rounding to float.  num_rhs = 0 writes an all-zero d_grad_mats (the empty sum).  A problem whose
+ * status != SIP_LQR_SUCCESS gets an all-zero gradient from the first group and is left alone by the later ones; its
+ * columns (unspecified, possibly NaN) are not read.  Every scalar of d_grad_mats is written exactly once per group;
+ * d_grad_mats need only be aligned to its scalar.  SIP_LQR_VJP_MULTI_COLUMNS=<1..8> (a measuring aid, read per call)
+ * caps the columns of a group.
+ *
+ * sip_lqr_vjp_multi is the whole backward pass in the plan's dtype against the factor state of the last
+ * sip_lqr_factor() on d_workspace, in this order: sip_lqr_solve_multi with the d_grad_sol_cols (g_c) as right-hand
+ * sides into d_grad_vecs_cols (lambda_c = dL/dvecs_c); where d_status is given, all-zero lambda_c of every failed
+ * problem in every column; then the kernel above on d_sol_cols and d_grad_vecs_cols, unless d_grad_mats is NULL (only
+ * the lambda_c are wanted).
+ *   d_col_workspace: sip_lqr_solve_multi_workspace_bytes(plan, num_rhs) of device scratch; may be NULL where that is 0.
+ * What sip_lqr_vjp says about sip_lqr_factor, the k part of d_gains, the gains and second derivatives holds here too.
+ *
+ * Both: kernels only, no allocation and no synchronisation, asynchronous on `stream`, safe under stream capture.
+ * SIP_LQR_ERR_INVALID_ARGUMENT, before any HIP call: a NULL plan, num_rhs < 0, num_rhs > 0 with a NULL column array
+ * (d_sol_cols, d_adj_cols, d_grad_sol_cols); sip_lqr_vjp_mats_multi: a NULL d_grad_mats, a `wide` that is neither 0
+ * nor 1; sip_lqr_vjp_multi: a NULL d_mats, d_workspace or d_grad_vecs_cols (d_gains when T > 0), a NULL
+ * d_col_workspace where its bytes are not 0. */
+int sip_lqr_vjp_multi_columns(const sip_lqr_plan *plan);
+int sip_lqr_vjp_mats_multi(const sip_lqr_plan *plan, const void *d_sol_cols, const void *d_adj_cols, int num_rhs,
+                           int wide, const int32_t *d_status, void *d_grad_mats, void *stream);
+int sip_lqr_vjp_multi(const sip_lqr_plan *plan, const void *d_mats, const void *d_sol_cols,
+                      const void *d_grad_sol_cols, int num_rhs, void *d_gains, void *d_workspace,
+                      void *d_col_workspace, const int32_t *d_status, void *d_grad_vecs_cols, void *d_grad_mats,
+                      void *stream);
+
 /* ------------------------------------------------------------------------
  * General trees / per-node dimensions (the full Topology + Dimensions model
  * of lqr.hpp:5-64): the path behind the drop-in C++ `LQR` adapter

@@ -62,6 +62,9 @@ _SIGNATURES = {
                                             _P, _P, _P]),
     "sip_lqr_vjp_mats": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, _P, _P, _P]),
     "sip_lqr_vjp": (ctypes.c_int, [_P] * 10),
+    "sip_lqr_vjp_multi_columns": (ctypes.c_int, [_P]),
+    "sip_lqr_vjp_mats_multi": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, ctypes.c_int, _P, _P, _P]),
+    "sip_lqr_vjp_multi": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "sip_lqr_compile_topology": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_P] * 9),
     "sip_lqr_tree_plan_create": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P,
                                                 ctypes.c_int, _PP]),

@@ -1,5 +1,6 @@
-"""The solves as differentiable torch functions: sol = chain_lqr_solve(solver, mats, vecs) and
-output = tree_lqr_solve(solver, input).  The chain first; the tree twin follows the same scheme (below).
+"""The solves as differentiable torch functions: sol = chain_lqr_solve(solver, mats, vecs), sol_cols =
+chain_lqr_solve_multi(solver, mats, vecs_cols) and output = tree_lqr_solve(solver, input).  The chain first; the tree
+twin follows the same scheme (below).
 
 Forward is solver.factor(mats) + solver.solve(...); backward is one adjoint solve against that factorisation and the
 outer-product kernel (BatchedChainLQR.vjp, sip_lqr_vjp), all on the device.  The factor state lives in the solver's
@@ -41,6 +42,43 @@ def chain_lqr_solve(solver, mats, vecs, return_status=False):
     whose status is not SUCCESS has an unspecified sol and gets zero gradients."""
     sol, status = _ChainLQRSolve.apply(solver, mats, vecs)
     return (sol, status) if return_status else sol
+
+
+class _ChainLQRSolveMulti(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, solver, mats, vecs_cols):
+        gains, status = solver.factor(mats)
+        sol_cols = solver.solve_multi(mats, vecs_cols, gains)
+        ctx.solver = solver
+        ctx.generation = solver.factor_generation
+        ctx.save_for_backward(mats, sol_cols, gains)
+        status = status.clone()  # the solver's own buffer is rewritten by the next factor call
+        ctx.mark_non_differentiable(status)
+        return sol_cols, status
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_sol_cols, _grad_status):
+        solver = ctx.solver
+        mats, sol_cols, gains = ctx.saved_tensors
+        if solver.factor_generation != ctx.generation:  # someone factored since: the workspace is not ours any more
+            solver.factor(mats, gains)
+            ctx.generation = solver.factor_generation
+        want_mats = ctx.needs_input_grad[1]
+        grad_mats, grad_vecs_cols = solver.vjp_multi(mats, sol_cols, grad_sol_cols.contiguous(), gains,
+                                                     want_mats=want_mats)
+        return None, grad_mats, grad_vecs_cols if ctx.needs_input_grad[2] else None
+
+
+def chain_lqr_solve_multi(solver, mats, vecs_cols, return_status=False):
+    """sol_cols [num_rhs, batch, vecs_len] of `solver` (a BatchedChainLQR) on one mats and the right-hand sides
+    vecs_cols [num_rhs, batch, vecs_len], differentiable with respect to both.  Forward is solver.factor(mats) +
+    solver.solve_multi(...); backward is one solver.vjp_multi (sip_lqr_vjp_multi): one adjoint solve_multi, and the
+    gradient of mats summed over the columns in one kernel.  The factor_generation check is that of chain_lqr_solve.
+    return_status=True: (sol_cols, status), status the int32 factor statuses of this call (not differentiable); a
+    problem whose status is not SUCCESS has unspecified columns and gets zero gradients."""
+    sol_cols, status = _ChainLQRSolveMulti.apply(solver, mats, vecs_cols)
+    return (sol_cols, status) if return_status else sol_cols
 
 
 class _TreeLQRSolve(torch.autograd.Function):

@@ -401,6 +401,77 @@ class BatchedChainLQR:
             ctypes.c_void_p(stream.cuda_stream)), "sip_lqr_vjp")
         return grad_mats, grad_vecs
 
+    @property
+    def vjp_multi_columns(self):
+        """Columns one launch of vjp_mats_multi carries on this plan (sip_lqr_vjp_multi_columns)."""
+        return int(self._lib.sip_lqr_vjp_multi_columns(self._plan))
+
+    def _grad_mats(self, grad_mats, dtype):
+        s = self.shape
+        if grad_mats is None:
+            return torch.empty(self.batch, s.mats_len, dtype=dtype, device=self.device)
+        if grad_mats.dtype != dtype or grad_mats.device != self.device or not grad_mats.is_contiguous() \
+                or grad_mats.numel() != self.batch * s.mats_len:
+            raise ValueError(f"grad_mats: expected contiguous {dtype} [{self.batch}, {s.mats_len}] on {self.device}")
+        return grad_mats
+
+    def vjp_mats_multi(self, sol_cols, adj_cols, use_status=True, grad_mats=None, stream=None):
+        """dL/dmats [batch, mats_len] of a loss that reads several solutions against one `mats`: the sum over the
+        columns of vjp_mats, formed in the kernel (sip_lqr_vjp_mats_multi).  sol_cols / adj_cols are [num_rhs, batch,
+        vecs_len], both in the plan's dtype or both float64, and the gradient in that dtype.  One column gives the
+        bits of vjp_mats; no column gives zeros.  Problems whose factor status is not SUCCESS get zeros
+        (use_status=False: nothing is masked)."""
+        num_rhs = self._cols(sol_cols, "sol_cols", (self.dtype, torch.float64))
+        if self._cols(adj_cols, "adj_cols", (sol_cols.dtype,)) != num_rhs:
+            raise ValueError("adj_cols: as many columns as sol_cols")
+        wide = 1 if sol_cols.dtype == torch.float64 else 0
+        grad_mats = self._grad_mats(grad_mats, sol_cols.dtype)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_vjp_mats_multi(
+            self._plan, ctypes.c_void_p(sol_cols.data_ptr() if num_rhs else None),
+            ctypes.c_void_p(adj_cols.data_ptr() if num_rhs else None), num_rhs, wide,
+            ctypes.c_void_p(self.status.data_ptr() if use_status else None), ctypes.c_void_p(grad_mats.data_ptr()),
+            ctypes.c_void_p(stream.cuda_stream)), "sip_lqr_vjp_mats_multi")
+        return grad_mats
+
+    def vjp_multi(self, mats, sol_cols, grad_sol_cols, gains, want_mats=True, use_status=True, refine_iterations=0,
+                  stream=None):
+        """The backward pass of solve_multi against the last factor(): (grad_mats or None, grad_vecs_cols) of a loss
+        whose gradient with respect to sol_cols [num_rhs, batch, vecs_len] is grad_sol_cols.  grad_vecs_cols holds the
+        adjoints lambda_c (K lambda_c + grad_sol_c = 0, one solve_multi), grad_mats [batch, mats_len] the sum over the
+        columns of vjp's outer products, formed in one kernel.  refine_iterations = 0: one sip_lqr_vjp_multi call,
+        everything in the plan's dtype.  refine_iterations > 0: the lambda_c from refine_multi() on the float64
+        grad_sol_cols, the kernel on float64 columns, float64 gradients.  Problems whose factor status is not SUCCESS
+        get zeros (use_status=False: whatever their solve leaves)."""
+        s = self.shape
+        num_rhs = self._cols(sol_cols, "sol_cols", (self.dtype,))
+        if self._cols(grad_sol_cols, "grad_sol_cols", (self.dtype,)) != num_rhs:
+            raise ValueError("grad_sol_cols: as many columns as sol_cols")
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        if refine_iterations > 0:
+            grad_vecs_cols, _ = self.refine_multi(mats, grad_sol_cols.double().contiguous(), gains,
+                                                  iterations=refine_iterations, use_status=use_status, stream=stream)
+            grad_mats = self.vjp_mats_multi(sol_cols.double().contiguous(), grad_vecs_cols, use_status=use_status,
+                                            stream=stream) if want_mats else None
+            return grad_mats, grad_vecs_cols
+        grad_vecs_cols = torch.empty(num_rhs, self.batch, s.vecs_len, dtype=self.dtype, device=self.device)
+        grad_mats = self._grad_mats(None, self.dtype) if want_mats else None
+        need = self._lib.sip_lqr_solve_multi_workspace_bytes(self._plan, num_rhs)
+        if getattr(self, "_col_ws", None) is None or self._col_ws.numel() < need:
+            self._col_ws = torch.empty(max(1, need), dtype=torch.uint8, device=self.device)
+        _check(self._lib.sip_lqr_vjp_multi(
+            self._plan, self._ptr(mats, self.batch, s.mats_len, "mats"),
+            ctypes.c_void_p(sol_cols.data_ptr() if num_rhs else None),
+            ctypes.c_void_p(grad_sol_cols.data_ptr() if num_rhs else None), num_rhs,
+            self._ptr(gains, self.batch, s.gains_len, "gains"), ctypes.c_void_p(self.workspace.data_ptr()),
+            ctypes.c_void_p(self._col_ws.data_ptr()), ctypes.c_void_p(self.status.data_ptr() if use_status else None),
+            ctypes.c_void_p(grad_vecs_cols.data_ptr() if num_rhs else self._col_ws.data_ptr()),
+            ctypes.c_void_p(grad_mats.data_ptr() if want_mats else None),
+            ctypes.c_void_p(stream.cuda_stream)), "sip_lqr_vjp_multi")
+        return grad_mats, grad_vecs_cols
+
     def close(self):
         if getattr(self, "_plan", None):
             self._lib.sip_lqr_plan_destroy(self._plan)

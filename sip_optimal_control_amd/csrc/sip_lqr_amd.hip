@@ -21,6 +21,7 @@
 #include "qw16_table.hpp"
 #include "residual_launch.hpp"
 #include "stream_fill.hpp"
+#include "vjp_cols_launch.hpp"
 #include "vjp_launch.hpp"
 
 using sipamd::KernelEntry;
@@ -954,6 +955,56 @@ int sip_lqr_vjp(const sip_lqr_plan *plan, const void *d_mats, const void *d_sol,
     e = sipamd::vjp::launch_vjp(vjp_args(plan, d_sol, d_grad_vecs, false, d_status, d_grad_mats),
                                 (hipStream_t)stream);
   return report(e, "sip_lqr_vjp");
+}
+
+} // extern "C"
+
+// ---- the same for several columns: one adjoint solve_multi, and the columns summed in the kernel (chain_vjp_cols.hpp)
+extern "C" {
+
+int sip_lqr_vjp_multi_columns(const sip_lqr_plan *plan) {
+  return plan ? sipamd::vjp::cols_per_launch(plan->n, plan->m) : 0;
+}
+
+int sip_lqr_vjp_mats_multi(const sip_lqr_plan *plan, const void *d_sol_cols, const void *d_adj_cols, int num_rhs,
+                           int wide, const int32_t *d_status, void *d_grad_mats, void *stream) {
+  if (plan == nullptr || num_rhs < 0 || (num_rhs > 0 && (!d_sol_cols || !d_adj_cols)) || !d_grad_mats ||
+      (wide != 0 && wide != 1))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  OnPlanDevice on_device(plan, "sip_lqr_vjp_mats_multi");
+  if (on_device.rc != SIP_LQR_OK)
+    return on_device.rc;
+  return report(sipamd::vjp::launch_vjp_cols(vjp_args(plan, d_sol_cols, d_adj_cols, wide == 1, d_status, d_grad_mats),
+                                             num_rhs, (hipStream_t)stream),
+                "sip_lqr_vjp_mats_multi");
+}
+
+int sip_lqr_vjp_multi(const sip_lqr_plan *plan, const void *d_mats, const void *d_sol_cols,
+                      const void *d_grad_sol_cols, int num_rhs, void *d_gains, void *d_workspace,
+                      void *d_col_workspace, const int32_t *d_status, void *d_grad_vecs_cols, void *d_grad_mats,
+                      void *stream) {
+  if (plan == nullptr || num_rhs < 0 || !d_mats || !d_workspace || !d_grad_vecs_cols || (plan->T > 0 && !d_gains) ||
+      (num_rhs > 0 && (!d_sol_cols || !d_grad_sol_cols)) ||
+      (!d_col_workspace && sip_lqr_solve_multi_workspace_bytes(plan, num_rhs) > 0))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  // lambda_c: K lambda_c + g_c = 0 is the plan's solve_multi with the g columns as the right-hand sides
+  const int rc = sip_lqr_solve_multi(plan, d_mats, d_grad_sol_cols, d_grad_vecs_cols, num_rhs, d_gains, d_workspace,
+                                     d_col_workspace, stream);
+  if (rc != SIP_LQR_OK)
+    return rc;
+  if ((d_status == nullptr || num_rhs == 0) && d_grad_mats == nullptr)
+    return SIP_LQR_OK;
+  OnPlanDevice on_device(plan, "sip_lqr_vjp_multi");
+  if (on_device.rc != SIP_LQR_OK)
+    return on_device.rc;
+  hipError_t e = hipSuccess;
+  if (d_status != nullptr && num_rhs > 0) // whatever the solves left for a failed problem, in every column
+    e = sipamd::vjp::launch_mask_cols(num_rhs, (long)plan->batch, lens(plan).vecs, plan->dtype == SIP_LQR_F32,
+                                      d_status, d_grad_vecs_cols, (hipStream_t)stream);
+  if (e == hipSuccess && d_grad_mats != nullptr)
+    e = sipamd::vjp::launch_vjp_cols(vjp_args(plan, d_sol_cols, d_grad_vecs_cols, false, d_status, d_grad_mats),
+                                     num_rhs, (hipStream_t)stream);
+  return report(e, "sip_lqr_vjp_multi");
 }
 
 } // extern "C"
