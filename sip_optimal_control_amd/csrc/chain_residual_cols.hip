@@ -1,7 +1,7 @@
-// chain_residual_cols.hip -- instantiations and launchers of the multi-column chain KKT residual and of the column
-// form of the refinement update (chain_residual_cols.hpp), declared in residual_launch.hpp.  A translation unit of its
-// own, like chain_residual.hip.
-#include "chain_residual_cols.hpp"
+// chain_residual_cols.hip -- instantiations and launchers of the chain KKT residual and of the refinement update
+// (chain_residual.hpp), for one column and for several, declared in residual_launch.hpp.  A translation unit of its
+// own: compiled in parallel with the others, and the solve kernels keep their modules.
+#include "chain_residual.hpp"
 #include "residual_launch.hpp"
 
 namespace sipamd {
@@ -11,7 +11,7 @@ namespace {
 template <typename S, typename V, bool STAGED, int NC>
 hipError_t launch_cols_as(const Args &a, const Dims &d, const ColsShape &sh, int ncols, hipStream_t stream) {
   const int wave_bytes = (int)((sh.lds_bytes - cols_red_bytes(NC)) / sh.waves);
-  hipLaunchKernelGGL((chain_residual_cols_kernel<S, V, STAGED, NC>), dim3((unsigned)a.batch), dim3(kLanes * sh.waves),
+  hipLaunchKernelGGL((chain_residual_kernel<S, V, STAGED, NC>), dim3((unsigned)a.batch), dim3(kLanes * sh.waves),
                      sh.lds_bytes, stream, d, (const S *)a.mats, (const V *)a.vecs, (const V *)a.sol,
                      a.batch * d.vecs_len, a.batch, ncols, a.res, (S *)a.scaled, a.scale, a.norm, wave_bytes);
   return hipGetLastError();
@@ -74,10 +74,10 @@ hipError_t launch_update_cols(long cols, long batch, long len, bool f32, const v
   const long blocks = (cols * batch * len + 255) / 256;
   const dim3 grid((unsigned)(blocks < 1 ? 1 : (blocks > 16384 ? 16384 : blocks)));
   if (f32)
-    hipLaunchKernelGGL((refine_update_cols_kernel<float>), grid, dim3(256), 0, stream, cols, batch, len,
+    hipLaunchKernelGGL((refine_update_kernel<float>), grid, dim3(256), 0, stream, cols, batch, len,
                        (const float *)dvec, scale, status, sol64);
   else
-    hipLaunchKernelGGL((refine_update_cols_kernel<double>), grid, dim3(256), 0, stream, cols, batch, len,
+    hipLaunchKernelGGL((refine_update_kernel<double>), grid, dim3(256), 0, stream, cols, batch, len,
                        (const double *)dvec, scale, status, sol64);
   return hipGetLastError();
 }

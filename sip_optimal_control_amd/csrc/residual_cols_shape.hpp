@@ -1,13 +1,15 @@
-// residual_cols_shape.hpp -- the launch shape of the multi-column chain residual (chain_residual_cols.hpp): how many
-// columns one launch carries, how many wavefronts a workgroup has, whether the stage image goes through LDS, and the
-// dynamic LDS that takes.  Host arithmetic only: no HIP call and no kernel in here, so a host program can print the
-// decisions (tests/cpp/test_residual_cols_shape.cpp).  The kernel header includes it for the two sizes it shares.
+// residual_cols_shape.hpp -- the launch shape of the chain residual (chain_residual.hpp), for one column and for
+// several: how many columns one launch carries, how many wavefronts a workgroup has, whether the stage image goes
+// through LDS, and the dynamic LDS that takes.  The constants and sizes of the kernel's LDS are stated here and nowhere
+// else.  Host arithmetic only: no HIP call and no kernel in here, so a host program can print the decisions
+// (tests/cpp/test_residual_cols_shape.cpp).  The kernel header includes it for the sizes it shares.
 //
 // LDS of a workgroup: NC doubles per wavefront slot for the norms (kColsMaxWaves slots), then per wavefront
 //   z[k][c]   (4 n + m) NC doubles   x_i | y_i | u_i | x_{i+1} | y_{i+1}, the NC columns of one entry adjacent
 //   e[k][c]   (2 n + m) NC doubles   the row ends q_i | r_i | c_{i+1}
 //   delta     n doubles              delta_{i+1}, once: it belongs to mats, not to a column
-// padded to 16 bytes, then, when staged, the stage image exactly as the single-column kernel lays it out.
+// padded to 16 bytes, then, when staged, the stage image: the stage's scalars behind up to 16 / sizeof(S) - 1 scalars of
+// lead-in (the image starts at the 16-byte piece that holds the stage's first scalar), padded likewise.
 //
 // Rules: never more than 64 KiB; staged needs `mats` 16-byte aligned and the image plus NC vector sets to fit; staged
 // with fewer columns is preferred over unstaged with more; among the staged (or, failing those, the unstaged) column
@@ -34,7 +36,7 @@ namespace residual {
 constexpr int kColsMax = 8;      // columns of the widest instantiation; the instantiations are 1, 2, 4 and 8
 constexpr int kColsMaxWaves = 4; // wavefronts of a workgroup
 constexpr int kColsWantWaves = SIP_RESIDUAL_COLS_WANT_WAVES;
-constexpr size_t kColsLdsBudget = 64 * 1024;
+constexpr size_t kColsLdsBudget = 64 * 1024; // dynamic LDS a launch may ask for without raising the kernel's limit
 
 struct ColsShape {
   int columns; // of the instantiation that is launched: 1, 2, 4 or 8 (a shorter group masks the rest); 0: nothing fits
@@ -54,7 +56,7 @@ inline int cols_stage_scalars(const int n, const int m, const bool sym) {
   const int nq = sym ? n * (n + 1) / 2 : n * n, nr = sym ? m * (m + 1) / 2 : m * m;
   return nq + n + n * n + 2 * n * m + nr;
 }
-// the image behind up to one 16-byte piece of lead-in, padded to whole pieces (image_bytes of chain_residual.hpp)
+// the image behind up to one 16-byte piece of lead-in, padded to whole pieces
 inline size_t cols_image_bytes(const int stage_scalars, const int scalar_bytes) {
   return ((size_t)stage_scalars * scalar_bytes + 16 + 15) & ~(size_t)15;
 }

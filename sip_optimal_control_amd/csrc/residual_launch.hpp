@@ -1,6 +1,6 @@
 // residual_launch.hpp -- the launchers of the KKT residual and of the refinement update on the packed chain layout
-// (chain_residual.hpp, instantiated in chain_residual.hip, a translation unit of its own).  No kernel source in here:
-// the host code (sip_lqr_amd.hip) includes this header alone.
+// (chain_residual.hpp, instantiated in chain_residual_cols.hip, a translation unit of its own).  No kernel source in
+// here: the host code (sip_lqr_amd.hip) includes this header alone.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,29 +28,15 @@ struct Args {
   double *norm;
 };
 
-// Waves of a workgroup and dynamic LDS bytes of one launch; staged: the stage's blocks go through LDS.
-struct Shape {
-  int waves;
-  bool staged;
-  size_t lds_bytes;
-};
-Shape launch_shape(const Args &a);
-
-hipError_t launch_residual(const Args &a, hipStream_t stream);
-
-// sol64[p] += scale[p] * d[p] (d in the plan's dtype, `len` scalars per problem) where status == nullptr or
-// status[p] == SIP_LQR_SUCCESS
-hipError_t launch_update(long batch, long len, bool f32, const void *d, const double *scale, const int32_t *status,
-                         double *sol64, hipStream_t stream);
-
-// The column form (chain_residual_cols.hpp, instantiated in chain_residual_cols.hip).  `a` describes column 0: vecs,
-// sol, res and scaled are [num_cols][batch][vecs_len] arrays (sip_lqr_solve_multi's layout), norm and scale
-// [num_cols][batch].  The columns go in groups of cols_launch_shape(a, kColsMax).columns, one launch per group, a
-// short last group on the least instantiation that holds it.
+// `a` describes column 0: vecs, sol, res and scaled are [num_cols][batch][vecs_len] arrays (sip_lqr_solve_multi's
+// layout), norm and scale [num_cols][batch]; the single-column entry points pass num_cols = 1.  The columns go in
+// groups of cols_launch_shape(a, kColsMax).columns, one launch per group, a short last group on the least
+// instantiation that holds it.
 ColsShape cols_launch_shape(const Args &a, int requested);
 hipError_t launch_residual_cols(const Args &a, int num_cols, hipStream_t stream);
 
-// sol64[c][p] += scale[c][p] * d[c][p] where status == nullptr or status[p] == SIP_LQR_SUCCESS (status per problem)
+// sol64[c][p] += scale[c][p] * d[c][p] (d in the plan's dtype, `len` scalars per problem and column) where
+// status == nullptr or status[p] == SIP_LQR_SUCCESS (status per problem)
 hipError_t launch_update_cols(long cols, long batch, long len, bool f32, const void *d, const double *scale,
                               const int32_t *status, double *sol64, hipStream_t stream);
 

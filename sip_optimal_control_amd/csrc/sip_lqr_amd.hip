@@ -737,21 +737,26 @@ int sip_lqr_solve_multi(const sip_lqr_plan *plan, const void *d_mats, const void
 
 } // extern "C"
 
-// ---- the residual of the chain KKT system and the refinement around the plan's solve (chain_residual.hpp) ----------
+// ---- the residual of the chain KKT system and the refinement around the plan's solve (chain_residual.hpp), for one
+// ---- column (sip_lqr_residual, sip_lqr_refine) and for several (sip_lqr_residual_multi, sip_lqr_refine_multi) -------
 namespace {
-// The regions of sip_lqr_refine's scratch, in bytes: rho / s and d in the plan's dtype, then s.
+// The regions of the refinement's scratch, in bytes: rho / s and d as [num_rhs][batch][vecs_len] in the plan's dtype,
+// then s[c][p].
 struct RefineWorkspace {
   size_t rho = 0, d = 0, scale = 0, total = 0;
 };
-RefineWorkspace refine_layout(const sip_lqr_plan *p) {
+RefineWorkspace refine_multi_layout(const sip_lqr_plan *p, int num_rhs) {
   auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t vec = up((size_t)p->batch * (size_t)lens(p).vecs * scalar_size(p));
+  const size_t cols = num_rhs < 1 ? 0 : (size_t)num_rhs;
+  const size_t vec = up(cols * (size_t)p->batch * (size_t)lens(p).vecs * scalar_size(p));
   RefineWorkspace w;
   w.d = vec;
   w.scale = 2 * vec;
-  w.total = w.scale + up((size_t)p->batch * sizeof(double));
+  w.total = w.scale + up(cols * (size_t)p->batch * sizeof(double));
   return w;
 }
+RefineWorkspace refine_layout(const sip_lqr_plan *p) { return refine_multi_layout(p, 1); }
+
 sipamd::residual::Args residual_args(const sip_lqr_plan *p, const void *mats, const void *vecs, const void *sol,
                                      bool wide) {
   sipamd::residual::Args a{};
@@ -761,6 +766,37 @@ sipamd::residual::Args residual_args(const sip_lqr_plan *p, const void *mats, co
   a.symmetric = p->layout == SIP_LQR_LAYOUT_SYMMETRIC;
   a.mats = mats, a.vecs = vecs, a.sol = sol;
   return a;
+}
+
+// The rounds of sip_lqr_refine and sip_lqr_refine_multi: scaled residual, solve(rho / s, d) -- the caller's solve of
+// num_rhs columns, returning a SIP_LQR_* code --, sol64 += s d; then one plain residual for the norms of the result.
+template <typename Solve>
+int refine_rounds(const sip_lqr_plan *plan, const void *d_mats, const double *d_vecs64, double *d_sol64, int num_rhs,
+                  int iterations, int from_zero, void *d_refine_workspace, const int32_t *d_status, double *d_norms,
+                  hipStream_t s, const char *what, Solve solve) {
+  const RefineWorkspace f = refine_multi_layout(plan, num_rhs);
+  char *w = (char *)d_refine_workspace;
+  double *scale = (double *)(w + f.scale);
+  const long B = (long)plan->batch, len = lens(plan).vecs;
+  const size_t row = (size_t)num_rhs * B; // norms of one round
+  sipamd::residual::Args a = residual_args(plan, d_mats, d_vecs64, d_sol64, true);
+  hipError_t e = from_zero ? sipamd::zero_async(d_sol64, row * len * sizeof(double), s) : hipSuccess;
+  for (int j = 0; j < iterations && e == hipSuccess; ++j) {
+    a.scaled = w + f.rho, a.scale = scale, a.norm = d_norms + (size_t)j * row;
+    e = sipamd::residual::launch_residual_cols(a, num_rhs, s);
+    if (e != hipSuccess)
+      break;
+    const int rc = solve(w + f.rho, w + f.d);
+    if (rc != SIP_LQR_OK)
+      return rc;
+    e = sipamd::residual::launch_update_cols(num_rhs, B, len, plan->dtype == SIP_LQR_F32, w + f.d, scale, d_status,
+                                             d_sol64, s);
+  }
+  if (e == hipSuccess) { // the norms of the result
+    a.scaled = nullptr, a.scale = nullptr, a.norm = d_norms + (size_t)iterations * row;
+    e = sipamd::residual::launch_residual_cols(a, num_rhs, s);
+  }
+  return report(e, what);
 }
 } // namespace
 
@@ -776,7 +812,7 @@ int sip_lqr_residual(const sip_lqr_plan *plan, const void *d_mats, const void *d
   sipamd::residual::Args a = residual_args(plan, d_mats, d_vecs, d_sol, wide == 1);
   a.res = d_res;
   a.norm = d_norm;
-  return report(sipamd::residual::launch_residual(a, (hipStream_t)stream), "sip_lqr_residual");
+  return report(sipamd::residual::launch_residual_cols(a, 1, (hipStream_t)stream), "sip_lqr_residual");
 }
 
 size_t sip_lqr_refine_workspace_bytes(const sip_lqr_plan *plan) { return plan ? refine_layout(plan).total : 0; }
@@ -787,51 +823,14 @@ int sip_lqr_refine(const sip_lqr_plan *plan, const void *d_mats, const double *d
   if (plan == nullptr || !d_mats || !d_vecs64 || !d_sol64 || !d_workspace || !d_refine_workspace || !d_norms ||
       (plan->T > 0 && !d_gains) || iterations < 1 || iterations > 32 || (from_zero != 0 && from_zero != 1))
     return SIP_LQR_ERR_INVALID_ARGUMENT;
-  hipStream_t s = (hipStream_t)stream;
   OnPlanDevice on_device(plan, "sip_lqr_refine");
   if (on_device.rc != SIP_LQR_OK)
     return on_device.rc;
-  const RefineWorkspace f = refine_layout(plan);
-  char *w = (char *)d_refine_workspace;
-  double *scale = (double *)(w + f.scale);
-  const long B = (long)plan->batch, len = lens(plan).vecs;
-  sipamd::residual::Args a = residual_args(plan, d_mats, d_vecs64, d_sol64, true);
-  hipError_t e = from_zero ? sipamd::zero_async(d_sol64, (size_t)B * len * sizeof(double), s) : hipSuccess;
-  for (int j = 0; j < iterations && e == hipSuccess; ++j) {
-    a.scaled = w + f.rho, a.scale = scale, a.norm = d_norms + (size_t)j * B;
-    e = sipamd::residual::launch_residual(a, s);
-    if (e != hipSuccess)
-      break;
-    const int rc = sip_lqr_solve(plan, d_mats, w + f.rho, w + f.d, d_gains, d_workspace, stream);
-    if (rc != SIP_LQR_OK)
-      return rc;
-    e = sipamd::residual::launch_update(B, len, plan->dtype == SIP_LQR_F32, w + f.d, scale, d_status, d_sol64, s);
-  }
-  if (e == hipSuccess) { // the norm of the result
-    a.scaled = nullptr, a.scale = nullptr, a.norm = d_norms + (size_t)iterations * B;
-    e = sipamd::residual::launch_residual(a, s);
-  }
-  return report(e, "sip_lqr_refine");
+  return refine_rounds(plan, d_mats, d_vecs64, d_sol64, 1, iterations, from_zero, d_refine_workspace, d_status, d_norms,
+                       (hipStream_t)stream, "sip_lqr_refine", [&](const void *rho, void *d) {
+                         return sip_lqr_solve(plan, d_mats, rho, d, d_gains, d_workspace, stream);
+                       });
 }
-
-} // extern "C"
-
-// ---- the same for several columns (chain_residual_cols.hpp) ---------------------------------------------------------
-namespace {
-// sip_lqr_refine_multi's scratch: rho / s and d as [num_rhs][batch][vecs_len] in the plan's dtype, then s[c][p].
-RefineWorkspace refine_multi_layout(const sip_lqr_plan *p, int num_rhs) {
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t cols = num_rhs < 1 ? 0 : (size_t)num_rhs;
-  const size_t vec = up(cols * (size_t)p->batch * (size_t)lens(p).vecs * scalar_size(p));
-  RefineWorkspace w;
-  w.d = vec;
-  w.scale = 2 * vec;
-  w.total = w.scale + up(cols * (size_t)p->batch * sizeof(double));
-  return w;
-}
-} // namespace
-
-extern "C" {
 
 int sip_lqr_residual_multi_columns(const sip_lqr_plan *plan) {
   if (plan == nullptr)
@@ -873,34 +872,14 @@ int sip_lqr_refine_multi(const sip_lqr_plan *plan, const void *d_mats, const dou
     return SIP_LQR_ERR_INVALID_ARGUMENT;
   if (num_rhs == 0)
     return SIP_LQR_OK;
-  hipStream_t s = (hipStream_t)stream;
   OnPlanDevice on_device(plan, "sip_lqr_refine_multi");
   if (on_device.rc != SIP_LQR_OK)
     return on_device.rc;
-  const RefineWorkspace f = refine_multi_layout(plan, num_rhs);
-  char *w = (char *)d_refine_workspace;
-  double *scale = (double *)(w + f.scale);
-  const long B = (long)plan->batch, len = lens(plan).vecs;
-  const size_t row = (size_t)num_rhs * B; // norms of one round
-  sipamd::residual::Args a = residual_args(plan, d_mats, d_vecs64_cols, d_sol64_cols, true);
-  hipError_t e = from_zero ? sipamd::zero_async(d_sol64_cols, row * len * sizeof(double), s) : hipSuccess;
-  for (int j = 0; j < iterations && e == hipSuccess; ++j) {
-    a.scaled = w + f.rho, a.scale = scale, a.norm = d_norms + (size_t)j * row;
-    e = sipamd::residual::launch_residual_cols(a, num_rhs, s);
-    if (e != hipSuccess)
-      break;
-    const int rc =
-        sip_lqr_solve_multi(plan, d_mats, w + f.rho, w + f.d, num_rhs, d_gains, d_workspace, d_col_workspace, stream);
-    if (rc != SIP_LQR_OK)
-      return rc;
-    e = sipamd::residual::launch_update_cols(num_rhs, B, len, plan->dtype == SIP_LQR_F32, w + f.d, scale, d_status,
-                                             d_sol64_cols, s);
-  }
-  if (e == hipSuccess) { // the norms of the result
-    a.scaled = nullptr, a.scale = nullptr, a.norm = d_norms + (size_t)iterations * row;
-    e = sipamd::residual::launch_residual_cols(a, num_rhs, s);
-  }
-  return report(e, "sip_lqr_refine_multi");
+  return refine_rounds(plan, d_mats, d_vecs64_cols, d_sol64_cols, num_rhs, iterations, from_zero, d_refine_workspace,
+                       d_status, d_norms, (hipStream_t)stream, "sip_lqr_refine_multi", [&](const void *rho, void *d) {
+                         return sip_lqr_solve_multi(plan, d_mats, rho, d, num_rhs, d_gains, d_workspace,
+                                                    d_col_workspace, stream);
+                       });
 }
 
 } // extern "C"

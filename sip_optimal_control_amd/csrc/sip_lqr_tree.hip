@@ -16,7 +16,6 @@
 #include "table_packer.hpp"
 #include "tree_plan.hpp"
 #include "tree_residual_cols_launch.hpp"
-#include "tree_residual_launch.hpp"
 #include "tree_vjp_launch.hpp"
 #include "vjp_launch.hpp"
 
@@ -30,8 +29,7 @@ struct sip_lqr_tree_plan {
   sipamd::TreeSchedule sched{};
   void *d_steps = nullptr;
   sipamd::TreeScratch scratch; // of the fused kernels: padded gains at 0, then the spill
-  sipamd::residual::TreeShape residual; // of the residual kernel: staged or in place, wavefronts, LDS
-  sipamd::residual::TreeColsDims residual_cols; // what the launch shape of its column form reads of the plan
+  sipamd::residual::TreeColsDims residual_cols; // what the launch shape of the residual kernel reads of the plan
   void *d_vjp_table = nullptr; // of the gradient kernel (tree_vjp_table.hpp): one word per input-arena scalar
   ~sip_lqr_tree_plan() {
     if (d_steps != nullptr)
@@ -127,8 +125,6 @@ int sip_lqr_tree_plan_create(int64_t batch, int num_edges, int root,
   hipError_t e = g.upload(device);
   if (e == hipSuccess)
     e = upload_vjp_table(p);
-  p->residual = sipamd::residual::tree_launch_shape(N, E, g.state_dims.data(), g.control_dims.data(), g.parents.data(),
-                                                    g.children.data());
   p->residual_cols = sipamd::residual::tree_cols_dims(N, E, g.state_dims.data(), g.control_dims.data(),
                                                       g.parents.data(), g.children.data());
   // size class of the fused kernels; where one holds the tree: its schedule and its scratch
@@ -342,93 +338,16 @@ const char *sip_lqr_tree_split_kernel_name(const sip_lqr_tree_plan *plan) {
   return plan->fused != nullptr ? plan->fused->split_name : "tree_generic/f64";
 }
 
-// ---- the residual of the tree KKT system and the refinement around the plan's solve (tree_residual.hpp) -----------
+// ---- the residual of the tree KKT system and the refinement around the plan's solve (tree_residual.hpp), for one
+// ---- column (sip_lqr_tree_residual, sip_lqr_tree_refine) and for several (..._multi) --------------------------------
 } // extern "C"
 
 namespace {
-// The regions of sip_lqr_tree_refine's scratch, in bytes: rho / s, d, s, then the scratch of the one-column solve.
+// The regions of the refinement's scratch, in bytes: rho / s and d as [num_rhs][batch][rhs_len], s[c][p], then the
+// scratch of the solve of num_rhs columns.
 struct TreeRefineWorkspace {
   size_t d = 0, scale = 0, solve = 0, total = 0; // rho / s is at 0
 };
-TreeRefineWorkspace tree_refine_layout(const sip_lqr_tree_plan *p) {
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t vec = up((size_t)p->batch * (size_t)p->g.out_len * sizeof(double));
-  TreeRefineWorkspace w;
-  w.d = vec;
-  w.scale = 2 * vec;
-  w.solve = w.scale + up((size_t)p->batch * sizeof(double));
-  w.total = w.solve + up(sip_lqr_tree_solve_multi_scratch_bytes(p, 1));
-  return w;
-}
-} // namespace
-
-extern "C" {
-
-const char *sip_lqr_tree_residual_kernel_name(const sip_lqr_tree_plan *plan) {
-  if (plan == nullptr)
-    return "";
-  return plan->residual.staged ? "tree_residual<staged>/f64" : "tree_residual<direct>/f64";
-}
-
-int sip_lqr_tree_residual(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_rhs,
-                          const double *d_output, double *d_res, double *d_norm, void *stream) {
-  if (plan == nullptr || d_norm == nullptr || missing_input(plan, d_input) || missing_output(plan, d_output) ||
-      plan->topology_status != SIP_LQR_SUCCESS)
-    return SIP_LQR_ERR_INVALID_ARGUMENT;
-  OnPlanDevice dev(plan, stream);
-  if (dev.rc != SIP_LQR_OK)
-    return dev.rc;
-  sipamd::residual::TreeArgs a{};
-  a.batch = (long)plan->batch, a.input = d_input, a.rhs = d_rhs, a.sol = d_output;
-  a.res = d_res, a.norm = d_norm;
-  return report(sipamd::residual::launch_tree_residual(plan->g.meta, plan->residual, a, dev.s),
-                "sip_lqr_tree_residual");
-}
-
-size_t sip_lqr_tree_refine_workspace_bytes(const sip_lqr_tree_plan *plan) {
-  return plan != nullptr && plan->topology_status == SIP_LQR_SUCCESS ? tree_refine_layout(plan).total : 0;
-}
-
-int sip_lqr_tree_refine(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_work, const double *d_rhs,
-                        double *d_output, int iterations, int from_zero, const int32_t *d_status,
-                        void *d_refine_workspace, double *d_norms, void *stream) {
-  if (plan == nullptr || d_status == nullptr || d_work == nullptr || d_refine_workspace == nullptr ||
-      d_norms == nullptr || missing_input(plan, d_input) || missing_output(plan, d_output) || iterations < 1 ||
-      iterations > 32 || (from_zero != 0 && from_zero != 1) || plan->topology_status != SIP_LQR_SUCCESS)
-    return SIP_LQR_ERR_INVALID_ARGUMENT;
-  OnPlanDevice dev(plan, stream);
-  if (dev.rc != SIP_LQR_OK)
-    return dev.rc;
-  const TreeRefineWorkspace f = tree_refine_layout(plan);
-  char *w = (char *)d_refine_workspace;
-  double *rho = (double *)w, *d = (double *)(w + f.d), *scale = (double *)(w + f.scale);
-  const long B = (long)plan->batch, len = plan->g.out_len;
-  sipamd::residual::TreeArgs a{};
-  a.batch = B, a.input = d_input, a.rhs = d_rhs, a.sol = d_output;
-  hipError_t e = from_zero ? sipamd::zero_async(d_output, (size_t)B * len * sizeof(double), dev.s) : hipSuccess;
-  for (int j = 0; j < iterations && e == hipSuccess; ++j) {
-    a.scaled = rho, a.scale = scale, a.norm = d_norms + (size_t)j * B;
-    e = sipamd::residual::launch_tree_residual(plan->g.meta, plan->residual, a, dev.s);
-    if (e != hipSuccess)
-      break;
-    // (an empty output arena: rho and d have no entries, and the solve's check of them does not apply)
-    const int rc = sip_lqr_tree_solve_multi(plan, d_input, d_work, rho, d, 1, d_status, w + f.solve, stream);
-    if (rc != SIP_LQR_OK)
-      return rc;
-    e = sipamd::residual::launch_update(B, len, false, d, scale, d_status, d_output, dev.s);
-  }
-  if (e == hipSuccess) { // the norm of the result
-    a.scaled = nullptr, a.scale = nullptr, a.norm = d_norms + (size_t)iterations * B;
-    e = sipamd::residual::launch_tree_residual(plan->g.meta, plan->residual, a, dev.s);
-  }
-  return report(e, "sip_lqr_tree_refine");
-}
-
-} // extern "C"
-
-// ---- the same for several columns (tree_residual_cols.hpp) ----------------------------------------------------------
-namespace {
-// sip_lqr_tree_refine_multi's scratch: rho / s and d as [num_rhs][batch][rhs_len], s[c][p], then the solve's scratch.
 TreeRefineWorkspace tree_refine_multi_layout(const sip_lqr_tree_plan *p, int num_rhs) {
   auto up = [](size_t v) { return (v + 255) / 256 * 256; };
   const size_t cols = (size_t)num_rhs;
@@ -440,65 +359,31 @@ TreeRefineWorkspace tree_refine_multi_layout(const sip_lqr_tree_plan *p, int num
   w.total = w.solve + up(sip_lqr_tree_solve_multi_scratch_bytes(p, num_rhs));
   return w;
 }
-sipamd::residual::TreeColsShape full_group(const sip_lqr_tree_plan *p) {
-  return sipamd::residual::tree_cols_shape(p->residual_cols, true, sipamd::residual::kTreeColsMax);
+TreeRefineWorkspace tree_refine_layout(const sip_lqr_tree_plan *p) { return tree_refine_multi_layout(p, 1); }
+
+sipamd::residual::TreeColsShape residual_shape(const sip_lqr_tree_plan *p, int requested) {
+  return sipamd::residual::tree_cols_shape(p->residual_cols, true, requested);
 }
 bool valid_plan(const sip_lqr_tree_plan *p) { return p != nullptr && p->topology_status == SIP_LQR_SUCCESS; }
-} // namespace
 
-extern "C" {
-
-int sip_lqr_tree_residual_multi_columns(const sip_lqr_tree_plan *plan) {
-  return valid_plan(plan) ? full_group(plan).columns : 0;
-}
-
-const char *sip_lqr_tree_residual_multi_kernel_name(const sip_lqr_tree_plan *plan) {
-  if (!valid_plan(plan)) // (a latched topology: no launch, no kernel)
-    return "";
-  static const char *const names[2][4] = {
-      {"tree_residual_cols<direct,1>/f64", "tree_residual_cols<direct,2>/f64", "tree_residual_cols<direct,4>/f64",
-       "tree_residual_cols<direct,8>/f64"},
-      {"tree_residual_cols<staged,1>/f64", "tree_residual_cols<staged,2>/f64", "tree_residual_cols<staged,4>/f64",
-       "tree_residual_cols<staged,8>/f64"}};
-  const sipamd::residual::TreeColsShape sh = full_group(plan);
-  const int k = sh.columns >= 8 ? 3 : (sh.columns >= 4 ? 2 : (sh.columns >= 2 ? 1 : 0));
-  // (one column per launch: the single-column kernel, staged where that kernel is)
-  return names[(sh.columns > 1 ? sh.staged : plan->residual.staged) ? 1 : 0][k];
-}
-
-int sip_lqr_tree_residual_multi(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_rhs_cols,
-                                const double *d_out_cols, int num_rhs, double *d_res_cols, double *d_norms,
-                                void *stream) {
-  if (plan == nullptr || d_norms == nullptr || num_rhs < 0 || missing_input(plan, d_input) ||
-      (num_rhs > 0 && missing_output(plan, d_out_cols)) || plan->topology_status != SIP_LQR_SUCCESS)
-    return SIP_LQR_ERR_INVALID_ARGUMENT;
-  if (num_rhs == 0)
-    return SIP_LQR_OK;
+// sip_lqr_tree_residual and sip_lqr_tree_residual_multi behind their checks
+int tree_residual(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_rhs_cols,
+                  const double *d_out_cols, int num_rhs, double *d_res_cols, double *d_norms, void *stream,
+                  const char *what) {
   OnPlanDevice dev(plan, stream);
   if (dev.rc != SIP_LQR_OK)
     return dev.rc;
   sipamd::residual::TreeColsArgs a{};
   a.batch = (long)plan->batch, a.input = d_input, a.rhs_cols = d_rhs_cols, a.sol_cols = d_out_cols;
   a.res = d_res_cols, a.norm = d_norms;
-  return report(sipamd::residual::launch_tree_residual_cols(plan->g.meta, plan->residual_cols, plan->residual, a,
-                                                            num_rhs, dev.s),
-                "sip_lqr_tree_residual_multi");
+  return report(sipamd::residual::launch_tree_residual_cols(plan->g.meta, plan->residual_cols, a, num_rhs, dev.s), what);
 }
 
-size_t sip_lqr_tree_refine_multi_workspace_bytes(const sip_lqr_tree_plan *plan, int num_rhs) {
-  return valid_plan(plan) && num_rhs >= 1 ? tree_refine_multi_layout(plan, num_rhs).total : 0;
-}
-
-int sip_lqr_tree_refine_multi(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_work,
-                              const double *d_rhs_cols, double *d_out_cols, int num_rhs, int iterations, int from_zero,
-                              const int32_t *d_status, void *d_refine_workspace, double *d_norms, void *stream) {
-  if (plan == nullptr || d_status == nullptr || d_work == nullptr || d_refine_workspace == nullptr ||
-      d_norms == nullptr || num_rhs < 0 || missing_input(plan, d_input) ||
-      (num_rhs > 0 && missing_output(plan, d_out_cols)) || iterations < 1 || iterations > 32 ||
-      (from_zero != 0 && from_zero != 1) || plan->topology_status != SIP_LQR_SUCCESS)
-    return SIP_LQR_ERR_INVALID_ARGUMENT;
-  if (num_rhs == 0)
-    return SIP_LQR_OK;
+// sip_lqr_tree_refine and sip_lqr_tree_refine_multi behind their checks: `iterations` rounds of scaled residual,
+// sip_lqr_tree_solve_multi on rho / s, out += s d; then one plain residual for the norms of the result.
+int tree_refine(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_work, const double *d_rhs_cols,
+                double *d_out_cols, int num_rhs, int iterations, int from_zero, const int32_t *d_status,
+                void *d_refine_workspace, double *d_norms, void *stream, const char *what) {
   OnPlanDevice dev(plan, stream);
   if (dev.rc != SIP_LQR_OK)
     return dev.rc;
@@ -510,8 +395,7 @@ int sip_lqr_tree_refine_multi(const sip_lqr_tree_plan *plan, const double *d_inp
   sipamd::residual::TreeColsArgs a{};
   a.batch = B, a.input = d_input, a.rhs_cols = d_rhs_cols, a.sol_cols = d_out_cols;
   auto residual = [&]() {
-    return sipamd::residual::launch_tree_residual_cols(plan->g.meta, plan->residual_cols, plan->residual, a, num_rhs,
-                                                       dev.s);
+    return sipamd::residual::launch_tree_residual_cols(plan->g.meta, plan->residual_cols, a, num_rhs, dev.s);
   };
   hipError_t e = from_zero ? sipamd::zero_async(d_out_cols, row * len * sizeof(double), dev.s) : hipSuccess;
   for (int j = 0; j < iterations && e == hipSuccess; ++j) {
@@ -529,7 +413,87 @@ int sip_lqr_tree_refine_multi(const sip_lqr_tree_plan *plan, const double *d_inp
     a.scaled = nullptr, a.scale = nullptr, a.norm = d_norms + (size_t)iterations * row;
     e = residual();
   }
-  return report(e, "sip_lqr_tree_refine_multi");
+  return report(e, what);
+}
+} // namespace
+
+extern "C" {
+
+const char *sip_lqr_tree_residual_kernel_name(const sip_lqr_tree_plan *plan) {
+  if (plan == nullptr)
+    return "";
+  // (a latched topology: its dimensions were never read, and the name stays the one such a plan always reported)
+  return valid_plan(plan) && residual_shape(plan, 1).staged ? "tree_residual<staged>/f64" : "tree_residual<direct>/f64";
+}
+
+int sip_lqr_tree_residual(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_rhs,
+                          const double *d_output, double *d_res, double *d_norm, void *stream) {
+  if (plan == nullptr || d_norm == nullptr || missing_input(plan, d_input) || missing_output(plan, d_output) ||
+      plan->topology_status != SIP_LQR_SUCCESS)
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  return tree_residual(plan, d_input, d_rhs, d_output, 1, d_res, d_norm, stream, "sip_lqr_tree_residual");
+}
+
+size_t sip_lqr_tree_refine_workspace_bytes(const sip_lqr_tree_plan *plan) {
+  return valid_plan(plan) ? tree_refine_layout(plan).total : 0;
+}
+
+int sip_lqr_tree_refine(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_work, const double *d_rhs,
+                        double *d_output, int iterations, int from_zero, const int32_t *d_status,
+                        void *d_refine_workspace, double *d_norms, void *stream) {
+  if (plan == nullptr || d_status == nullptr || d_work == nullptr || d_refine_workspace == nullptr ||
+      d_norms == nullptr || missing_input(plan, d_input) || missing_output(plan, d_output) || iterations < 1 ||
+      iterations > 32 || (from_zero != 0 && from_zero != 1) || plan->topology_status != SIP_LQR_SUCCESS)
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  return tree_refine(plan, d_input, d_work, d_rhs, d_output, 1, iterations, from_zero, d_status, d_refine_workspace,
+                     d_norms, stream, "sip_lqr_tree_refine");
+}
+
+int sip_lqr_tree_residual_multi_columns(const sip_lqr_tree_plan *plan) {
+  return valid_plan(plan) ? residual_shape(plan, sipamd::residual::kTreeColsMax).columns : 0;
+}
+
+const char *sip_lqr_tree_residual_multi_kernel_name(const sip_lqr_tree_plan *plan) {
+  if (!valid_plan(plan)) // (a latched topology: no launch, no kernel)
+    return "";
+  static const char *const names[2][4] = {
+      {"tree_residual_cols<direct,1>/f64", "tree_residual_cols<direct,2>/f64", "tree_residual_cols<direct,4>/f64",
+       "tree_residual_cols<direct,8>/f64"},
+      {"tree_residual_cols<staged,1>/f64", "tree_residual_cols<staged,2>/f64", "tree_residual_cols<staged,4>/f64",
+       "tree_residual_cols<staged,8>/f64"}};
+  const sipamd::residual::TreeColsShape sh = residual_shape(plan, sipamd::residual::kTreeColsMax);
+  const int k = sh.columns >= 8 ? 3 : (sh.columns >= 4 ? 2 : (sh.columns >= 2 ? 1 : 0));
+  return names[sh.staged ? 1 : 0][k];
+}
+
+int sip_lqr_tree_residual_multi(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_rhs_cols,
+                                const double *d_out_cols, int num_rhs, double *d_res_cols, double *d_norms,
+                                void *stream) {
+  if (plan == nullptr || d_norms == nullptr || num_rhs < 0 || missing_input(plan, d_input) ||
+      (num_rhs > 0 && missing_output(plan, d_out_cols)) || plan->topology_status != SIP_LQR_SUCCESS)
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  if (num_rhs == 0)
+    return SIP_LQR_OK;
+  return tree_residual(plan, d_input, d_rhs_cols, d_out_cols, num_rhs, d_res_cols, d_norms, stream,
+                       "sip_lqr_tree_residual_multi");
+}
+
+size_t sip_lqr_tree_refine_multi_workspace_bytes(const sip_lqr_tree_plan *plan, int num_rhs) {
+  return valid_plan(plan) && num_rhs >= 1 ? tree_refine_multi_layout(plan, num_rhs).total : 0;
+}
+
+int sip_lqr_tree_refine_multi(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_work,
+                              const double *d_rhs_cols, double *d_out_cols, int num_rhs, int iterations, int from_zero,
+                              const int32_t *d_status, void *d_refine_workspace, double *d_norms, void *stream) {
+  if (plan == nullptr || d_status == nullptr || d_work == nullptr || d_refine_workspace == nullptr ||
+      d_norms == nullptr || num_rhs < 0 || missing_input(plan, d_input) ||
+      (num_rhs > 0 && missing_output(plan, d_out_cols)) || iterations < 1 || iterations > 32 ||
+      (from_zero != 0 && from_zero != 1) || plan->topology_status != SIP_LQR_SUCCESS)
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  if (num_rhs == 0)
+    return SIP_LQR_OK;
+  return tree_refine(plan, d_input, d_work, d_rhs_cols, d_out_cols, num_rhs, iterations, from_zero, d_status,
+                     d_refine_workspace, d_norms, stream, "sip_lqr_tree_refine_multi");
 }
 
 } // extern "C"

@@ -1,6 +1,7 @@
-// tree_residual_cols.hip -- instantiations and launcher of the multi-column tree KKT residual (tree_residual_cols.hpp),
-// declared in tree_residual_cols_launch.hpp.  A translation unit of its own, like tree_residual.hip.
-#include "tree_residual_cols.hpp"
+// tree_residual_cols.hip -- instantiations and launcher of the tree KKT residual (tree_residual.hpp), for one column
+// and for several, declared in tree_residual_cols_launch.hpp.  A translation unit of its own: compiled in parallel with
+// the others, and the solve kernels keep their modules.
+#include "tree_residual.hpp"
 #include "tree_residual_cols_launch.hpp"
 
 namespace sipamd {
@@ -13,7 +14,7 @@ hipError_t launch_cols_as(const tree::Meta &meta, const TreeColsShape &sh, const
   const size_t fixed =
       tree_cols_red_bytes(NC) + (SPLIT ? tree_cols_parts_bytes(meta.num_nodes, meta.num_edges, meta.max_n, NC) : 0);
   const int wave_bytes = (int)((sh.lds_bytes - fixed) / sh.waves);
-  hipLaunchKernelGGL((tree_residual_cols_kernel<STAGED, SPLIT, NC>), dim3((unsigned)a.batch), dim3(kLanes * sh.waves),
+  hipLaunchKernelGGL((tree_residual_kernel<STAGED, SPLIT, NC>), dim3((unsigned)a.batch), dim3(kLanes * sh.waves),
                      sh.lds_bytes, stream, meta, a.input, a.rhs_cols, a.sol_cols, a.batch * meta.out_len, a.batch, ncols,
                      a.res, a.scaled, a.scale, a.norm, wave_bytes);
   return hipGetLastError();
@@ -22,7 +23,8 @@ hipError_t launch_cols_as(const tree::Meta &meta, const TreeColsShape &sh, const
 template <bool STAGED, bool SPLIT>
 hipError_t launch_cols_instance(const tree::Meta &meta, const TreeColsShape &sh, const TreeColsArgs &a, int ncols,
                                 hipStream_t stream) {
-  switch (sh.columns) { // (a group of one column goes to the single-column kernel: no instantiation for it)
+  switch (sh.columns) {
+  case 1: return launch_cols_as<STAGED, SPLIT, 1>(meta, sh, a, ncols, stream);
   case 2: return launch_cols_as<STAGED, SPLIT, 2>(meta, sh, a, ncols, stream);
   case 4: return launch_cols_as<STAGED, SPLIT, 4>(meta, sh, a, ncols, stream);
   case 8: return launch_cols_as<STAGED, SPLIT, 8>(meta, sh, a, ncols, stream);
@@ -38,8 +40,8 @@ hipError_t launch_cols_form(const tree::Meta &meta, const TreeColsShape &sh, con
 }
 } // namespace
 
-hipError_t launch_tree_residual_cols(const tree::Meta &meta, const TreeColsDims &dims, const TreeShape &single,
-                                     const TreeColsArgs &a, int num_cols, hipStream_t stream) {
+hipError_t launch_tree_residual_cols(const tree::Meta &meta, const TreeColsDims &dims, const TreeColsArgs &a,
+                                     int num_cols, hipStream_t stream) {
   if (num_cols < 1 || a.batch < 1 || a.batch > 0x7fffffffL || (a.scaled != nullptr && a.scale == nullptr))
     return hipErrorInvalidValue;
   // the image is copied by 16-byte pieces from the piece that holds the item's first scalar: input must be aligned
@@ -57,18 +59,11 @@ hipError_t launch_tree_residual_cols(const tree::Meta &meta, const TreeColsDims 
     g.scaled = a.scaled ? a.scaled + c0 * stride : nullptr;
     g.scale = a.scale ? a.scale + (size_t)c0 * a.batch : nullptr;
     g.norm = a.norm + (size_t)c0 * a.batch;
-    hipError_t e;
-    if (nc == 1) {
-      TreeArgs one{};
-      one.batch = g.batch, one.input = g.input, one.rhs = g.rhs_cols, one.sol = g.sol_cols;
-      one.res = g.res, one.scaled = g.scaled, one.scale = g.scale, one.norm = g.norm;
-      e = launch_tree_residual(meta, single, one, stream);
-    } else {
-      const TreeColsShape sh = tree_cols_shape(dims, aligned, nc);
-      if (sh.columns < nc || sh.waves < 1)
-        return hipErrorInvalidValue;
-      e = sh.staged ? launch_cols_form<true>(meta, sh, g, nc, stream) : launch_cols_form<false>(meta, sh, g, nc, stream);
-    }
+    const TreeColsShape sh = tree_cols_shape(dims, aligned, nc);
+    if (sh.columns < nc || sh.waves < 1)
+      return hipErrorInvalidValue;
+    const hipError_t e =
+        sh.staged ? launch_cols_form<true>(meta, sh, g, nc, stream) : launch_cols_form<false>(meta, sh, g, nc, stream);
     if (e != hipSuccess)
       return e;
   }

@@ -1,7 +1,8 @@
-// tree_residual_cols_launch.hpp -- the launcher of the multi-column KKT residual on the tree-native arenas
-// (tree_residual_cols.hpp, instantiated in tree_residual_cols.hip, a translation unit of its own).  No kernel source in
-// here: the host code (sip_lqr_tree.hip) includes this header, tree_residual_launch.hpp and residual_launch.hpp alone.
-// The launch shape is host arithmetic in tree_residual_cols_shape.hpp.
+// tree_residual_cols_launch.hpp -- the launcher of the KKT residual on the tree-native arenas, for one column and for
+// several (tree_residual.hpp, instantiated in tree_residual_cols.hip, a translation unit of its own).  The refinement
+// update is the chain's (residual_launch.hpp: launch_update_cols).  No kernel source in here: the host code
+// (sip_lqr_tree.hip) includes this header and residual_launch.hpp alone.  The launch shape is host arithmetic in
+// tree_residual_cols_shape.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,7 +11,6 @@
 
 #include "tree_generic.hpp"
 #include "tree_residual_cols_shape.hpp"
-#include "tree_residual_launch.hpp"
 
 namespace sipamd {
 namespace residual {
@@ -26,10 +26,10 @@ struct TreeColsArgs {
 };
 
 // The columns go in groups of tree_cols_shape(dims, aligned, kTreeColsMax).columns, one launch per group, a short last
-// group on the least instantiation that holds it and a group of one column on the single-column kernel (`single`: what
-// the plan decided for launch_tree_residual), whose bits the column kernel gives.
-hipError_t launch_tree_residual_cols(const tree::Meta &meta, const TreeColsDims &dims, const TreeShape &single,
-                                     const TreeColsArgs &a, int num_cols, hipStream_t stream);
+// group on the least instantiation that holds it; the single-column entry points pass num_cols = 1.  A staged plan
+// whose `input` is not 16-byte aligned is served by the in-place instantiations.
+hipError_t launch_tree_residual_cols(const tree::Meta &meta, const TreeColsDims &dims, const TreeColsArgs &a,
+                                     int num_cols, hipStream_t stream);
 
 } // namespace residual
 } // namespace sipamd

@@ -1,15 +1,17 @@
-// tree_residual_cols_shape.hpp -- the launch shape of the multi-column tree residual (tree_residual_cols.hpp): how many
-// columns one launch carries, how many wavefronts a workgroup has, whether the matrices of an item go through LDS,
-// whether the wavefronts take nodes and edges alike (split), and the dynamic LDS that takes.  Host arithmetic only: no
-// HIP call and no kernel in here, so a host program can print the decisions (tests/cpp/test_tree_residual_cols_shape.cpp).
-// The kernel header includes it for the sizes it shares.
+// tree_residual_cols_shape.hpp -- the launch shape of the tree residual (tree_residual.hpp), for one column and for
+// several: how many columns one launch carries, how many wavefronts a workgroup has, whether the matrices of an item go
+// through LDS, whether the wavefronts take nodes and edges alike (split), and the dynamic LDS that takes.  What the
+// rules read of a plan, the constants and the sizes of the kernel's LDS are stated here and nowhere else.  Host
+// arithmetic only: no HIP call and no kernel in here, so a host program can print the decisions
+// (tests/cpp/test_tree_residual_cols_shape.cpp).  The kernel header includes it for the sizes it shares.
 //
 // LDS of a workgroup: NC doubles per wavefront slot for the norms (kTreeColsMaxWaves slots), then per wavefront
 //   node part   x_i | y_i | q_i | acc head | acc tail        5 max_n NC doubles, z[k][c]: the NC columns of an entry adjacent
 //   edge part   x_p | u | x_c | y_c | r | c_c                (4 max_n + 2 max_m) NC doubles, packed by the edge's dims
 //   delta_c     max_n doubles, once: it belongs to the input arena, not to a column
-// padded to 16 bytes, then, when staged, the image of the largest item exactly as the single-column kernel lays it out;
-// behind the wavefronts, in the split form, the parts: head | tail, max_n NC doubles each, per node and per edge.
+// padded to 16 bytes, then, when staged, the image of the largest item: its doubles behind at most one of lead-in,
+// padded likewise; behind the wavefronts, in the split form, the parts: head | tail, max_n NC doubles each, per node
+// and per edge.
 //
 // Rules:
 //   never more than 64 KiB;
@@ -17,8 +19,11 @@
 //   staged with fewer columns is taken before unstaged with more;
 //   the widest instantiation tried is the least of 1, 2, 4, 8 that holds the requested columns, so a short group is
 //   never launched on one twice as wide as it needs;
-//   split is wanted where the single-column rule wants it (max_children * 4 > N + E) and is taken at a column count
-//   only where the parts and two wavefronts fit there (with one wavefront it shares nothing out);
+//   split is wanted where one node's children alone outnumber a wavefront's even share of all items
+//   (max_children * 4 > N + E: there nodes in turn leave the other wavefronts idle, measured 2x on a root with 63
+//   children; elsewhere they are faster by 14 %, with no second gather of the parent's x and no barrier: DESIGN
+//   4.10.1) and is taken at a column count only where the parts and two wavefronts fit there (with one wavefront it
+//   shares nothing out);
 //   where split is wanted and kTreeColsPreferSplit is set, the largest column count at which split can be taken wins
 //   over a larger one with nodes in turn; where it is not set, the largest column count that fits with nodes in turn
 //   wins, and runs split only if split can be taken at that very count;
@@ -34,7 +39,7 @@
 #define SIP_TREE_COLS_HD
 #endif
 
-// 1: where the single-column rule wants the split form, fewer columns split are taken before more columns with nodes
+// 1: where the split form is wanted, fewer columns split are taken before more columns with nodes
 // in turn.  Measured on the reference's shallow wide tree (63 children of the root, 8 columns): split
 // with 2 columns a launch beats nodes in turn with 8, which a build with 0 here gives, at batch 4096 and at 1024.
 #ifndef SIP_TREE_RESIDUAL_COLS_PREFER_SPLIT
@@ -95,7 +100,7 @@ SIP_TREE_COLS_HD inline size_t tree_cols_parts_bytes(const int num_nodes, const 
                                                      const int nc) {
   return (size_t)(num_nodes + num_edges) * 2 * (size_t)max_n * (size_t)nc * sizeof(double);
 }
-// the image behind at most one scalar of lead-in, padded to whole pieces (tree_image_bytes of tree_residual.hpp)
+// the image behind at most one scalar of lead-in, padded to whole pieces
 inline size_t tree_cols_image_bytes(const long scalars) { return ((size_t)scalars * 8 + 16 + 15) & ~(size_t)15; }
 
 // The instantiation that carries `requested` columns: the least of 1, 2, 4, 8 that holds them.

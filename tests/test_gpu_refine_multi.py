@@ -1,5 +1,5 @@
 """sip_lqr_residual_multi and sip_lqr_refine_multi on the GPU (BatchedChainLQR.residual_multi / .refine_multi;
-csrc/chain_residual_cols.hpp).
+csrc/chain_residual.hpp).
 
 Residual: every column against the formulas in np.longdouble (refine_cases.residual), every entry held to the derived
 bound (2 n + m + 3) 2^-53 a and every norm to the largest of those bounds, as tests/test_gpu_refine.py holds the

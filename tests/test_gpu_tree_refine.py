@@ -164,6 +164,32 @@ def test_residual_against_numpy(name, with_rhs):
     assert with_rhs or not np.array_equal(own[0], other[0])   # the column is not the problem's own q, c, r
 
 
+@pytest.mark.parametrize("name", ["five_node", "star_of_12"], ids=["nodes_in_turn", "split"])
+def test_an_input_that_is_not_16_byte_aligned_is_read_in_place(name):
+    """A staged plan whose d_input sits 8 bytes off a 16-byte boundary is served by the in-place instantiations, in
+    both forms: against long double under the same bound, and the bits of the aligned call."""
+    topo, blocks, rhs, sol, _, (ref, mag) = _draw(name)
+    s, maps = _plan(topo, 3)
+    assert s.residual_kernel_name == STAGED
+    _load(s, maps, topo, blocks)
+    L, out, col = topo.layout.sol_len, _dev(sol), _dev(maps.pack_rhs(s, rhs))
+    res, norm = s.residual(out, rhs=col)
+    torch.cuda.synchronize()
+    aligned, norm_aligned = _host(res, L).copy(), norm.cpu().numpy().copy()
+    room = torch.zeros(s.input.numel() + 2, dtype=torch.float64, device="cuda:0")
+    assert room.data_ptr() % 16 == 0
+    off = room[1:1 + s.input.numel()].view(s.batch, -1)
+    off.copy_(s.input)
+    assert off.data_ptr() % 16 == 8 and off.is_contiguous()
+    s.input = off
+    res, norm = s.residual(out, rhs=col)
+    torch.cuda.synchronize()
+    got, norm = _host(res, L), norm.cpu().numpy()
+    _check_residual(topo, got, norm, ref, mag, name + " misaligned")
+    np.testing.assert_array_equal(got, aligned)
+    np.testing.assert_array_equal(norm, norm_aligned)
+
+
 def test_residual_of_every_problem_of_a_batch_beyond_the_cus():
     """300 distinct problems, more workgroups than compute units: every problem's norm and vector."""
     build = lambda: tc.batched(tc.reference_trees()["five_node"], 300, seed=9)

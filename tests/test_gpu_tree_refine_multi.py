@@ -1,5 +1,5 @@
 """sip_lqr_tree_residual_multi and sip_lqr_tree_refine_multi on the GPU (BatchedTreeLQR.residual_multi / .refine_multi;
-csrc/tree_residual_cols.hpp).
+csrc/tree_residual.hpp).
 
 Residual: every column against the formulas in np.longdouble (tree_refine_cases.residual), every entry held to the
 derived bound |got - ref| <= k 2^-53 a and every norm to the largest bound of its problem and column, as
@@ -123,8 +123,8 @@ CASES.update({
                    "tree_factor_solve_qw16", COUNTS),
     # never split: the parts exceed LDS at one column.  Three columns keep the host reference short.
     "parts_beyond_lds": (lambda: _wide_and_deep(), _name(True, 8), "tree_factor_solve_qw16<15,", (3,)),
-    # split, and its parts (127 items) fit at 2 columns only: four launches carry 8 columns, and 9 end on the
-    # single-column kernel (csrc/tree_residual_cols_shape.hpp prefers that to nodes in turn at 8 columns: DESIGN 4.10.3)
+    # split, and its parts (127 items) fit at 2 columns only: four launches carry 8 columns, and 9 end on a launch of
+    # one column (csrc/tree_residual_cols_shape.hpp prefers that to nodes in turn at 8 columns: DESIGN 4.10.3)
     "shallow_wide_63": (lambda: _shallow_wide(), _name(True, 2), "tree_factor_solve_qw16", (2, 3, 8, 9)),
 })
 _DRAWS = {}

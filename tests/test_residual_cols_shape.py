@@ -1,4 +1,5 @@
-"""The launch shape of the multi-column chain residual (csrc/residual_cols_shape.hpp), without a GPU: the host program
+"""The launch shape of the chain residual, for one column and for several (csrc/residual_cols_shape.hpp), without a GPU:
+the host program
 tests/cpp/test_residual_cols_shape.cpp prints columns, wavefronts, staged and LDS bytes for a fixed list of shapes, and
 every line is recomputed here from the rules the header states:
 
@@ -24,7 +25,8 @@ def _image_bytes(n, m, f32, sym):
 
 
 def _single_column_stages(n, m, f32, sym, aligned):
-    """Whether chain_residual.hip's launch_shape stages this plan (kRedBytes = 32, z_doubles = 7 n + 2 m)."""
+    """Where one column stages: exactly where the rule the single-column kernel had of its own staged (32 bytes for the
+    norms, 7 n + 2 m doubles of vectors and the image within 64 KiB, `mats` aligned)."""
     z = ((7 * n + 2 * m + 1) // 2 * 2) * 8
     return aligned and z + _image_bytes(n, m, f32, sym) <= BUDGET - 32
 
