@@ -781,6 +781,61 @@ int sip_lqr_tree_vjp(const sip_lqr_tree_plan *plan, const double *d_input, const
                      const double *d_output, const double *d_grad_output, const int32_t *d_status, double *d_adj,
                      double *d_grad_input, void *d_scratch, void *stream);
 
+/* Gradients through sip_lqr_tree_solve_multi: several columns against ONE input arena, and one gradient (the tree twin
+ * of sip_lqr_vjp_multi).  Column c solves K z_c + b_c = 0 with the caller's right-hand side b_c; a loss that reads
+ * every z_c has dL/d(A, B, M, R, Q, delta) = sum over c of the table above on (lambda_c, z_c), with lambda_c the adjoint
+ * of column c, and dL/db_c = lambda_c.  Columns are laid out as for sip_lqr_tree_solve_multi: column c at
+ * c * batch * sip_lqr_tree_output_len() doubles; there is one d_grad_input of batch * sip_lqr_tree_input_len() doubles.
+ *
+ * sip_lqr_tree_vjp_input_multi is the kernel alone.  An entry of a matrix block or of delta is, over the columns in
+ * ascending order and in fp64, fma(lambda_0[ia], z_0[ib], z_0[ia] * lambda_0[ib]) for the first column and
+ * acc = fma(lambda_c[ia], z_c[ib], fma(z_c[ia], lambda_c[ib], acc)) for every further one, then times 1, 1/2 or -1/2
+ * (exact) and one store.  THE q, c AND r SLOTS OF d_grad_input ARE WRITTEN +0.0: sip_lqr_tree_solve_multi ignores the
+ * arena's q, c, r (its right-hand sides are the columns), so the true gradient there is zero, and dL/db_c is lambda_c
+ * itself, which the caller holds as d_adj_cols.  One column therefore gives the bits of sip_lqr_tree_vjp_input on
+ * every other entry and +0.0 on these.  One launch carries sip_lqr_tree_vjp_multi_columns() columns: min(8, what 160 KiB
+ * of LDS hold at 16 * sip_lqr_tree_output_len() bytes per column; the kernel's limit of dynamic LDS is raised where a
+ * group needs more than 64 KiB), or 8 read in place where not even one column fits 64 KiB; more columns go in further
+ * launches, which read the scalar already in d_grad_input, undo its factor exactly and chain
+ * their columns onto it, so the result does not depend on the grouping (barring underflow in the halving).
+ * SIP_LQR_TREE_VJP_MULTI_COLUMNS=<1..8> caps the columns of a launch and SIP_LQR_TREE_VJP_COLS_SHAPE=<wavefronts>,
+ * <entries per run>[,<KiB of LDS, 0: read in place>] replaces the launch shape: measuring aids, read per call.
+ *   num_rhs : >= 0; 0 writes an all-zero gradient and reads no column;
+ *   d_status: NULL, or the statuses the factor call wrote: a problem whose status != SIP_LQR_SUCCESS gets an all-zero
+ *             gradient, and its columns (unspecified, possibly NaN) are not read.
+ * Every scalar of d_grad_input is written exactly once per launch and nothing else is; d_grad_input need only be
+ * aligned to 8 bytes; no atomics: two calls give the same bits.  An empty input arena launches nothing.
+ * sip_lqr_tree_vjp_multi_columns(): 0 for NULL or a latched invalid topology.  sip_lqr_tree_vjp_multi_kernel_name():
+ * "tree_vjp_cols<staged,NC>/f64" or "tree_vjp_cols<direct,NC>/f64" with NC the columns of a full launch; "" for NULL
+ * or a latched invalid topology.  Kernels only, no allocation, copy or synchronisation, asynchronous on `stream`, safe
+ * under stream capture.  SIP_LQR_ERR_INVALID_ARGUMENT, before any HIP call: a NULL plan, a latched invalid topology,
+ * num_rhs < 0, num_rhs > 0 with a NULL d_out_cols or d_adj_cols whose arena is not empty, a NULL d_grad_input.
+ *
+ * sip_lqr_tree_vjp_multi is the whole backward pass against the factor state in d_work (left by any of the three
+ * factor entry points; only read), on the fused size-class kernels and on the general engine alike: one
+ * sip_lqr_tree_solve_multi with the columns d_grad_out_cols (g_c = dL/dz_c) as right-hand sides into d_adj_cols
+ * (lambda_c = dL/db_c); every column of d_adj_cols zeroed where status != SIP_LQR_SUCCESS (the solve leaves those
+ * untouched); then the kernel above on d_out_cols and d_adj_cols.
+ *   d_status    : required; a failed problem ends with all-zero d_adj_cols and an all-zero d_grad_input;
+ *   d_grad_input: may be NULL: only the lambda_c are wanted, the kernel is not launched and d_out_cols is not needed;
+ *   d_scratch   : sip_lqr_tree_vjp_multi_scratch_bytes(plan, num_rhs) =
+ *                 sip_lqr_tree_solve_multi_scratch_bytes(plan, num_rhs) of device scratch (required even where that
+ *                 is 0);
+ *   num_rhs     : >= 0; 0 solves nothing and writes an all-zero d_grad_input.
+ * Kernels only, no allocation, copy or synchronisation, asynchronous on `stream`, safe under stream capture.
+ * SIP_LQR_ERR_INVALID_ARGUMENT, before any HIP call: a NULL plan, a latched invalid topology, num_rhs < 0, a NULL
+ * d_status, d_work or d_scratch, a NULL d_input whose arena is not empty, num_rhs > 0 with a NULL d_grad_out_cols or
+ * d_adj_cols whose arena is not empty, a NULL d_out_cols with d_grad_input given (and num_rhs > 0). */
+int sip_lqr_tree_vjp_multi_columns(const sip_lqr_tree_plan *plan);
+const char *sip_lqr_tree_vjp_multi_kernel_name(const sip_lqr_tree_plan *plan);
+int sip_lqr_tree_vjp_input_multi(const sip_lqr_tree_plan *plan, const double *d_out_cols, const double *d_adj_cols,
+                                 int num_rhs, const int32_t *d_status, double *d_grad_input, void *stream);
+size_t sip_lqr_tree_vjp_multi_scratch_bytes(const sip_lqr_tree_plan *plan, int num_rhs);
+int sip_lqr_tree_vjp_multi(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_work,
+                           const double *d_out_cols, const double *d_grad_out_cols, int num_rhs,
+                           const int32_t *d_status, double *d_adj_cols, double *d_grad_input, void *d_scratch,
+                           void *stream);
+
 /* Name of the kernel variant the plan dispatches to (static string). */
 const char *sip_lqr_kernel_name(const sip_lqr_plan *plan);
 

@@ -12,13 +12,14 @@ from .layout import ChainShape  # noqa: F401
 from .chain import BatchedChainLQR, FactorStatus  # noqa: F401
 from .kkt import BatchedNewtonKKT  # noqa: F401
 from . import synthetic  # noqa: F401
-from .autograd import chain_lqr_solve, chain_lqr_solve_multi, tree_lqr_solve  # noqa: F401
+from .autograd import chain_lqr_solve, chain_lqr_solve_multi, tree_lqr_solve, tree_lqr_solve_multi  # noqa: F401
 
 __all__ = [
     "BatchedChainLQR",
     "chain_lqr_solve",
     "chain_lqr_solve_multi",
     "tree_lqr_solve",
+    "tree_lqr_solve_multi",
     "BatchedNewtonKKT",
     "ChainShape",
     "FactorStatus",

@@ -100,6 +100,11 @@ _SIGNATURES = {
     "sip_lqr_tree_vjp_input": (ctypes.c_int, [_P] * 6),
     "sip_lqr_tree_vjp_scratch_bytes": (ctypes.c_size_t, [_P]),
     "sip_lqr_tree_vjp": (ctypes.c_int, [_P] * 10),
+    "sip_lqr_tree_vjp_multi_columns": (ctypes.c_int, [_P]),
+    "sip_lqr_tree_vjp_multi_kernel_name": (ctypes.c_char_p, [_P]),
+    "sip_lqr_tree_vjp_input_multi": (ctypes.c_int, [_P, _P, _P, ctypes.c_int, _P, _P, _P]),
+    "sip_lqr_tree_vjp_multi_scratch_bytes": (ctypes.c_size_t, [_P, ctypes.c_int]),
+    "sip_lqr_tree_vjp_multi": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P, _P]),
     "sip_lqr_tree_factor_fused": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "sip_lqr_tree_solve_fused": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "sip_lqr_tree_split_kernel_name": (ctypes.c_char_p, [_P]),

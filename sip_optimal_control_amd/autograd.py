@@ -1,6 +1,6 @@
 """The solves as differentiable torch functions: sol = chain_lqr_solve(solver, mats, vecs), sol_cols =
-chain_lqr_solve_multi(solver, mats, vecs_cols) and output = tree_lqr_solve(solver, input).  The chain first; the tree
-twin follows the same scheme (below).
+chain_lqr_solve_multi(solver, mats, vecs_cols), output = tree_lqr_solve(solver, input) and out_cols =
+tree_lqr_solve_multi(solver, input, rhs_cols).  The chain first; the tree twins follow the same scheme (below).
 
 Forward is solver.factor(mats) + solver.solve(...); backward is one adjoint solve against that factorisation and the
 outer-product kernel (BatchedChainLQR.vjp, sip_lqr_vjp), all on the device.  The factor state lives in the solver's
@@ -120,3 +120,45 @@ def tree_lqr_solve(solver, input, return_status=False):
     gradients.  The gains are not differentiated, and there is no second derivative."""
     output, status = _TreeLQRSolve.apply(solver, input)
     return (output, status) if return_status else output
+
+
+class _TreeLQRSolveMulti(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, solver, input, rhs_cols):
+        solver.input.copy_(input.detach().reshape(solver.input.shape))
+        solver.factor_fused()
+        out_cols = solver.solve_multi(rhs_cols.detach())
+        ctx.solver = solver
+        ctx.generation = solver.factor_generation
+        status = solver.status.clone()  # the solver's own buffer is rewritten by the next factor call
+        ctx.save_for_backward(input.detach().clone(), out_cols)
+        ctx.mark_non_differentiable(status)
+        return out_cols, status
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out_cols, _grad_status):
+        solver = ctx.solver
+        input, out_cols = ctx.saved_tensors
+        want_input, want_rhs = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if not (want_input or want_rhs):
+            return None, None, None
+        if solver.factor_generation != ctx.generation:  # someone packed or factored since: neither arena is ours
+            solver.input.copy_(input.reshape(solver.input.shape))
+            solver.factor_fused()
+            ctx.generation = solver.factor_generation
+        grad_input, adj_cols = solver.vjp_multi(grad_out_cols.contiguous(), out_cols, want_input=want_input)
+        return None, grad_input.reshape(input.shape) if want_input else None, adj_cols if want_rhs else None
+
+
+def tree_lqr_solve_multi(solver, input, rhs_cols, return_status=False):
+    """out_cols [num_rhs, batch, output_len] of `solver` (a BatchedTreeLQR) on one `input` [batch, in_len] (the input
+    arena) and the right-hand sides rhs_cols [num_rhs, batch, rhs_len] (pack_rhs), differentiable with respect to both.
+    Forward copies `input` into solver.input and runs factor_fused() + solve_multi(rhs_cols); backward is one
+    solver.vjp_multi (sip_lqr_tree_vjp_multi): one adjoint solve_multi, and the gradient of the input arena summed over
+    the columns in one kernel.  solve_multi does not read the arena's q, c, r, so their slots of the gradient are zero;
+    the gradient of rhs_cols is the adjoint columns.  The factor_generation check is that of tree_lqr_solve.
+    return_status=True: (out_cols, status), status the int32 factor statuses of this call (not differentiable); a
+    problem whose status is not SUCCESS has unspecified columns and gets zero gradients."""
+    out_cols, status = _TreeLQRSolveMulti.apply(solver, input, rhs_cols)
+    return (out_cols, status) if return_status else out_cols

@@ -16,7 +16,9 @@
 #include "table_packer.hpp"
 #include "tree_plan.hpp"
 #include "tree_residual_cols_launch.hpp"
+#include "tree_vjp_cols_launch.hpp"
 #include "tree_vjp_launch.hpp"
+#include "vjp_cols_launch.hpp"
 #include "vjp_launch.hpp"
 
 struct sip_lqr_tree_plan {
@@ -555,6 +557,73 @@ int sip_lqr_tree_vjp(const sip_lqr_tree_plan *plan, const double *d_input, const
   if (e == hipSuccess && d_grad_input != nullptr)
     e = sipamd::tree_vjp::launch_tree_vjp(tree_vjp_args(plan, d_output, d_adj, d_status, d_grad_input), dev.s);
   return report(e, "sip_lqr_tree_vjp");
+}
+
+// ---- several columns against one input arena, one gradient (tree_vjp_cols.hpp) -------------------------------------
+
+int sip_lqr_tree_vjp_multi_columns(const sip_lqr_tree_plan *plan) {
+  return valid_plan(plan) ? sipamd::tree_vjp::cols_per_launch(plan->g.out_len) : 0;
+}
+
+const char *sip_lqr_tree_vjp_multi_kernel_name(const sip_lqr_tree_plan *plan) {
+  if (!valid_plan(plan)) // (a latched topology: no table, no kernel)
+    return "";
+  static const char *const names[2][sipamd::tree_vjp::kColsMax] = {
+      {"tree_vjp_cols<direct,1>/f64", "tree_vjp_cols<direct,2>/f64", "tree_vjp_cols<direct,3>/f64",
+       "tree_vjp_cols<direct,4>/f64", "tree_vjp_cols<direct,5>/f64", "tree_vjp_cols<direct,6>/f64",
+       "tree_vjp_cols<direct,7>/f64", "tree_vjp_cols<direct,8>/f64"},
+      {"tree_vjp_cols<staged,1>/f64", "tree_vjp_cols<staged,2>/f64", "tree_vjp_cols<staged,3>/f64",
+       "tree_vjp_cols<staged,4>/f64", "tree_vjp_cols<staged,5>/f64", "tree_vjp_cols<staged,6>/f64",
+       "tree_vjp_cols<staged,7>/f64", "tree_vjp_cols<staged,8>/f64"}};
+  const int columns = sipamd::tree_vjp::cols_per_launch(plan->g.out_len);
+  const sipamd::tree_vjp::ColsShape sh =
+      sipamd::tree_vjp::cols_shape(plan->g.in0_len, plan->g.out_len, (long)plan->batch, columns);
+  return names[sh.at.staged ? 1 : 0][columns - 1];
+}
+
+int sip_lqr_tree_vjp_input_multi(const sip_lqr_tree_plan *plan, const double *d_out_cols, const double *d_adj_cols,
+                                 int num_rhs, const int32_t *d_status, double *d_grad_input, void *stream) {
+  if (!valid_plan(plan) || num_rhs < 0 || d_grad_input == nullptr ||
+      (num_rhs > 0 && (missing_output(plan, d_out_cols) || missing_output(plan, d_adj_cols))))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  OnPlanDevice dev(plan, stream);
+  if (dev.rc != SIP_LQR_OK)
+    return dev.rc;
+  return report(sipamd::tree_vjp::launch_tree_vjp_cols(tree_vjp_args(plan, d_out_cols, d_adj_cols, d_status, d_grad_input),
+                                                       num_rhs, dev.s),
+                "sip_lqr_tree_vjp_input_multi");
+}
+
+size_t sip_lqr_tree_vjp_multi_scratch_bytes(const sip_lqr_tree_plan *plan, int num_rhs) {
+  return sip_lqr_tree_solve_multi_scratch_bytes(plan, num_rhs);
+}
+
+int sip_lqr_tree_vjp_multi(const sip_lqr_tree_plan *plan, const double *d_input, const double *d_work,
+                           const double *d_out_cols, const double *d_grad_out_cols, int num_rhs,
+                           const int32_t *d_status, double *d_adj_cols, double *d_grad_input, void *d_scratch,
+                           void *stream) {
+  if (!valid_plan(plan) || num_rhs < 0 || d_status == nullptr || d_work == nullptr || d_scratch == nullptr ||
+      missing_input(plan, d_input) ||
+      (num_rhs > 0 && (missing_output(plan, d_grad_out_cols) || missing_output(plan, d_adj_cols) ||
+                       (d_grad_input != nullptr && missing_output(plan, d_out_cols)))))
+    return SIP_LQR_ERR_INVALID_ARGUMENT;
+  // lambda_c: K lambda_c + g_c = 0 is the plan's solve_multi with the g columns as the right-hand sides
+  if (num_rhs > 0) {
+    const int rc = sip_lqr_tree_solve_multi(plan, d_input, d_work, d_grad_out_cols, d_adj_cols, num_rhs, d_status,
+                                            d_scratch, stream);
+    if (rc != SIP_LQR_OK)
+      return rc;
+  }
+  OnPlanDevice dev(plan, stream);
+  if (dev.rc != SIP_LQR_OK)
+    return dev.rc;
+  hipError_t e = hipSuccess;
+  if (num_rhs > 0 && plan->g.out_len > 0) // the solve leaves a failed problem untouched, in every column
+    e = sipamd::vjp::launch_mask_cols(num_rhs, (long)plan->batch, plan->g.out_len, false, d_status, d_adj_cols, dev.s);
+  if (e == hipSuccess && d_grad_input != nullptr)
+    e = sipamd::tree_vjp::launch_tree_vjp_cols(tree_vjp_args(plan, d_out_cols, d_adj_cols, d_status, d_grad_input),
+                                               num_rhs, dev.s);
+  return report(e, "sip_lqr_tree_vjp_multi");
 }
 
 } // extern "C"

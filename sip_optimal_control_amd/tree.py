@@ -373,6 +373,65 @@ class BatchedTreeLQR:
                                           ctypes.c_void_p(s.cuda_stream)), "sip_lqr_tree_vjp")
         return grad, adj
 
+    @property
+    def vjp_multi_columns(self):
+        """Columns one launch of the multi-column gradient kernel carries on this plan
+        (sip_lqr_tree_vjp_multi_columns)."""
+        return int(self._lib.sip_lqr_tree_vjp_multi_columns(self._plan))
+
+    @property
+    def vjp_multi_kernel_name(self):
+        return self._lib.sip_lqr_tree_vjp_multi_kernel_name(self._plan).decode()
+
+    def vjp_input_multi(self, out_cols, adj_cols, use_status=True, grad_input=None):
+        """The multi-column gradient kernel alone (sip_lqr_tree_vjp_input_multi): ONE grad_input [batch, in_len] in the
+        input arena's layout (written to `grad_input` when given), the sum over the columns of out_cols (z_c) and
+        adj_cols (lambda_c), both [num_rhs, batch, output_len]; the q, c, r slots are +0.0 (solve_multi does not read
+        them: their gradient is adj_cols).  No column: zeros.  use_status: problems whose status != 0 get zeros."""
+        num_rhs = self._cols(out_cols, "out_cols")
+        if self._cols(adj_cols, "adj_cols") != num_rhs:
+            raise ValueError("adj_cols: as many columns as out_cols")
+        grad = grad_input if grad_input is not None else \
+            torch.empty(self.batch, max(1, self.in_len), dtype=torch.float64, device=self.device)
+        self._arena(grad, self.in_len, "grad_input")
+        s = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_tree_vjp_input_multi(
+            self._plan, ctypes.c_void_p(out_cols.data_ptr()), ctypes.c_void_p(adj_cols.data_ptr()), num_rhs,
+            ctypes.c_void_p(self.status.data_ptr() if use_status else None), ctypes.c_void_p(grad.data_ptr()),
+            ctypes.c_void_p(s.cuda_stream)), "sip_lqr_tree_vjp_input_multi")
+        return grad
+
+    def vjp_multi(self, grad_out_cols, out_cols, want_input=True, refine_iterations=0):
+        """The backward pass of solve_multi for a loss with dL/d(out_cols) = grad_out_cols [num_rhs, batch,
+        output_len], against the factor state in `work` (sip_lqr_tree_vjp_multi): one adjoint solve_multi,
+        K adj_c + grad_out_c = 0, then the multi-column kernel on out_cols and adj_cols.  Returns (grad_input [batch,
+        in_len], summed over the columns, +0.0 in the q, c, r slots, or None with want_input=False; adj_cols [num_rhs,
+        batch, output_len] = dL/d(rhs_cols)).  refine_iterations > 0: adj_cols comes from that many rounds of
+        refine_multi() on grad_out_cols from a zero iterate instead of the plain solve.  Problems whose status != 0
+        get zeros in both.  The gains are not differentiated."""
+        num_rhs = self._cols(grad_out_cols, "grad_out_cols")
+        if want_input and self._cols(out_cols, "out_cols") != num_rhs:
+            raise ValueError("out_cols: as many columns as grad_out_cols")
+        if int(refine_iterations) > 0:
+            adj = torch.zeros(num_rhs, self.batch, max(1, self.out_len), dtype=torch.float64, device=self.device)
+            self.refine_multi(grad_out_cols, iterations=int(refine_iterations), out_cols=adj)
+            adj.masked_fill_((self.status != 0).reshape(1, -1, 1), 0.0)
+            return (self.vjp_input_multi(out_cols, adj) if want_input else None), adj
+        adj = torch.empty(num_rhs, self.batch, max(1, self.out_len), dtype=torch.float64, device=self.device)
+        grad = torch.empty(self.batch, max(1, self.in_len), dtype=torch.float64, device=self.device) \
+            if want_input else None
+        need = self._lib.sip_lqr_tree_vjp_multi_scratch_bytes(self._plan, num_rhs)
+        if getattr(self, "_multi_scratch", None) is None or self._multi_scratch.numel() < need:
+            self._multi_scratch = torch.empty(max(1, need), dtype=torch.uint8, device=self.device)
+        s = torch.cuda.current_stream(self.device)
+        _check(self._lib.sip_lqr_tree_vjp_multi(
+            self._plan, ctypes.c_void_p(self.input.data_ptr()), ctypes.c_void_p(self.work.data_ptr()),
+            ctypes.c_void_p(out_cols.data_ptr() if want_input else None), ctypes.c_void_p(grad_out_cols.data_ptr()),
+            num_rhs, ctypes.c_void_p(self.status.data_ptr()), ctypes.c_void_p(adj.data_ptr()),
+            ctypes.c_void_p(grad.data_ptr() if want_input else None), ctypes.c_void_p(self._multi_scratch.data_ptr()),
+            ctypes.c_void_p(s.cuda_stream)), "sip_lqr_tree_vjp_multi")
+        return grad, adj
+
     def unpack_solution(self, b=0, output=None):
         out = (self.output[b] if output is None else output[b]).cpu().numpy()
         x, y, u = [], [], []
