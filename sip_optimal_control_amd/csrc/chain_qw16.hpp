@@ -456,7 +456,120 @@ struct StagedCfg {
   static constexpr int LDS_BYTES = LDS_MAIN + SCR_BYTES;
   static constexpr bool OK = N <= 16;
   static constexpr bool WIDE = N % 2 == 0; // columns of n scalars are 16-byte aligned in the images: 16-byte LDS accesses
+  // PARK (chain_factor_solve_qw16<..., PARK>): the spill slots of nodes 1 .. KEEP never reach HBM.  The rollout wants
+  // the four slots of a stage exactly as its LDS-DMA lands them -- the FW image: 4 * WSN * 8 bytes, lane-linear -- and
+  // that image is PARK_DW dwords per lane, held in accumulation registers between the two sweeps (the kernel runs
+  // one wavefront per SIMD and its arithmetic uses none of them).
+  static constexpr int PARK_IMG = 4 * WSN * 8;                    // bytes of a stage's spill image (3 264 at n = 12)
+  static constexpr int PARK_DW = (PARK_IMG + 255) / 256;          // dwords per lane of the image
+  static constexpr int PARK_B128 = PARK_IMG / 1024;               // lane-linear 16-byte reads; the rest is one dword
+  static constexpr int PARK_SPAN = PARK_B128 * 1024 + 256;        // bytes the lane-linear accesses cover
+  static constexpr int PARK_LDS = PARK_SPAN + 64 * 8;             // + one dump slot per lane for the masked-out writes
+  // 19 banks would fit 256 registers, but the compiler already spills the backward stage's values into this file
+  // (the plain kernel names 30 of them in the full layout and 58 in the symmetric-packed one, the parked kernel 40 and
+  // 60 of its own) and takes them from the registers no asm block names: 256 - 13 * 16 = 48 >= 40 and 256 - 13 * 15 =
+  // 61 >= 60 are the largest counts at which the build shows no scratch (17 and 16 banks leave 35 and 48).
+  static constexpr int KEEP = SYM ? 15 : 16;
+  static_assert(KEEP >= 1 && KEEP <= 19, "banks of 13 accumulation registers, SIP_PARK_BANKS");
+  static constexpr int PARK_AT = B_NBUF * B_BYTES;                // the backward sweep's image: behind its stage buffers
+  static constexpr bool PARK_OK = WPACK && !SPLIT && F_NBUF == 3 && PARK_DW == 13 && PARK_B128 == 3 &&
+                                  PARK_IMG - PARK_B128 * 1024 <= 256 && PARK_AT + PARK_LDS <= LDS_MAIN &&
+                                  PARK_SPAN <= FW::BYTES;
 };
+
+// The accumulation-register bank of parked node j = 1 .. 19: a[13 (j - 1)] .. a[13 (j - 1) + 12], as the clobber list
+// of the asm block that moves it (register numbers are literal in the instruction).
+// Nothing in the language tells the compiler that a bank stays live from the block that writes it to the block that
+// reads it: a clobber covers its own statement only.  What keeps the banks is a habit of this compiler -- it takes the
+// accumulation registers it spills to from those that no instruction of the function names -- and the test that holds
+// the shipped listing to it (tests/test_park_regs.py over tools/check_park_regs.py: no bank register named outside
+// the blocks' markers, no scratch).  That test is the guard; it has to pass again after every compiler upgrade.
+#define SIP_PARK_BANKS(X)                                                                                              \
+  X(1, "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", "a10", "a11", "a12")                                \
+  X(2, "a13", "a14", "a15", "a16", "a17", "a18", "a19", "a20", "a21", "a22", "a23", "a24", "a25")                      \
+  X(3, "a26", "a27", "a28", "a29", "a30", "a31", "a32", "a33", "a34", "a35", "a36", "a37", "a38")                      \
+  X(4, "a39", "a40", "a41", "a42", "a43", "a44", "a45", "a46", "a47", "a48", "a49", "a50", "a51")                      \
+  X(5, "a52", "a53", "a54", "a55", "a56", "a57", "a58", "a59", "a60", "a61", "a62", "a63", "a64")                      \
+  X(6, "a65", "a66", "a67", "a68", "a69", "a70", "a71", "a72", "a73", "a74", "a75", "a76", "a77")                      \
+  X(7, "a78", "a79", "a80", "a81", "a82", "a83", "a84", "a85", "a86", "a87", "a88", "a89", "a90")                      \
+  X(8, "a91", "a92", "a93", "a94", "a95", "a96", "a97", "a98", "a99", "a100", "a101", "a102", "a103")                  \
+  X(9, "a104", "a105", "a106", "a107", "a108", "a109", "a110", "a111", "a112", "a113", "a114", "a115", "a116")         \
+  X(10, "a117", "a118", "a119", "a120", "a121", "a122", "a123", "a124", "a125", "a126", "a127", "a128", "a129")        \
+  X(11, "a130", "a131", "a132", "a133", "a134", "a135", "a136", "a137", "a138", "a139", "a140", "a141", "a142")        \
+  X(12, "a143", "a144", "a145", "a146", "a147", "a148", "a149", "a150", "a151", "a152", "a153", "a154", "a155")        \
+  X(13, "a156", "a157", "a158", "a159", "a160", "a161", "a162", "a163", "a164", "a165", "a166", "a167", "a168")        \
+  X(14, "a169", "a170", "a171", "a172", "a173", "a174", "a175", "a176", "a177", "a178", "a179", "a180", "a181")        \
+  X(15, "a182", "a183", "a184", "a185", "a186", "a187", "a188", "a189", "a190", "a191", "a192", "a193", "a194")        \
+  X(16, "a195", "a196", "a197", "a198", "a199", "a200", "a201", "a202", "a203", "a204", "a205", "a206", "a207")        \
+  X(17, "a208", "a209", "a210", "a211", "a212", "a213", "a214", "a215", "a216", "a217", "a218", "a219", "a220")        \
+  X(18, "a221", "a222", "a223", "a224", "a225", "a226", "a227", "a228", "a229", "a230", "a231", "a232", "a233")        \
+  X(19, "a234", "a235", "a236", "a237", "a238", "a239", "a240", "a241", "a242", "a243", "a244", "a245", "a246")
+
+typedef unsigned park_u4 __attribute__((ext_vector_type(4)));
+// One lane's 13 dwords of a spill image (three 16-byte pieces and a dword, lane-linear).
+struct ParkRegs {
+  park_u4 q0, q1, q2;
+  unsigned tail;
+};
+// Image -> bank `node` (1 .. KEEP; wave-uniform).  The markers fence every accumulation-register reference of the
+// kernel for tools/check_park_regs.py: the compiler is to use none of its own.
+template <int KEEP>
+__device__ __forceinline__ void park_bank(const int node, const ParkRegs &r) {
+  switch (node) {
+#define SIP_PARK_WRITE(J, ...)                                                                                         \
+  case J:                                                                                                              \
+    if constexpr (J <= KEEP)                                                                                           \
+      asm volatile("; sip_park_begin\n\t"                                                                              \
+                   "v_accvgpr_write_b32 a[%13], %0\n\tv_accvgpr_write_b32 a[%13+1], %1\n\t"                            \
+                   "v_accvgpr_write_b32 a[%13+2], %2\n\tv_accvgpr_write_b32 a[%13+3], %3\n\t"                          \
+                   "v_accvgpr_write_b32 a[%13+4], %4\n\tv_accvgpr_write_b32 a[%13+5], %5\n\t"                          \
+                   "v_accvgpr_write_b32 a[%13+6], %6\n\tv_accvgpr_write_b32 a[%13+7], %7\n\t"                          \
+                   "v_accvgpr_write_b32 a[%13+8], %8\n\tv_accvgpr_write_b32 a[%13+9], %9\n\t"                          \
+                   "v_accvgpr_write_b32 a[%13+10], %10\n\tv_accvgpr_write_b32 a[%13+11], %11\n\t"                      \
+                   "v_accvgpr_write_b32 a[%13+12], %12\n\t"                                                            \
+                   "; sip_park_end" ::"v"(r.q0[0]),                                                                    \
+                   "v"(r.q0[1]), "v"(r.q0[2]), "v"(r.q0[3]), "v"(r.q1[0]), "v"(r.q1[1]), "v"(r.q1[2]), "v"(r.q1[3]),   \
+                   "v"(r.q2[0]), "v"(r.q2[1]), "v"(r.q2[2]), "v"(r.q2[3]), "v"(r.tail), "n"(13 * (J - 1))              \
+                   : __VA_ARGS__);                                                                                     \
+    break;
+    SIP_PARK_BANKS(SIP_PARK_WRITE)
+#undef SIP_PARK_WRITE
+  default:
+    break;
+  }
+}
+// Bank `node` -> registers.  The trailing s_nop keeps the reads clear of the LDS stores that take them as data.
+template <int KEEP>
+__device__ __forceinline__ void unpark_bank(const int node, ParkRegs &r) {
+  unsigned d[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  switch (node) {
+#define SIP_PARK_READ(J, ...)                                                                                          \
+  case J:                                                                                                              \
+    if constexpr (J <= KEEP)                                                                                           \
+      asm volatile("; sip_park_begin\n\t"                                                                              \
+                   "v_accvgpr_read_b32 %0, a[%13]\n\tv_accvgpr_read_b32 %1, a[%13+1]\n\t"                              \
+                   "v_accvgpr_read_b32 %2, a[%13+2]\n\tv_accvgpr_read_b32 %3, a[%13+3]\n\t"                            \
+                   "v_accvgpr_read_b32 %4, a[%13+4]\n\tv_accvgpr_read_b32 %5, a[%13+5]\n\t"                            \
+                   "v_accvgpr_read_b32 %6, a[%13+6]\n\tv_accvgpr_read_b32 %7, a[%13+7]\n\t"                            \
+                   "v_accvgpr_read_b32 %8, a[%13+8]\n\tv_accvgpr_read_b32 %9, a[%13+9]\n\t"                            \
+                   "v_accvgpr_read_b32 %10, a[%13+10]\n\tv_accvgpr_read_b32 %11, a[%13+11]\n\t"                        \
+                   "v_accvgpr_read_b32 %12, a[%13+12]\n\ts_nop 1\n\t"                                                  \
+                   "; sip_park_end"                                                                                    \
+                   : "=v"(d[0]), "=v"(d[1]), "=v"(d[2]), "=v"(d[3]), "=v"(d[4]), "=v"(d[5]), "=v"(d[6]), "=v"(d[7]),   \
+                     "=v"(d[8]), "=v"(d[9]), "=v"(d[10]), "=v"(d[11]), "=v"(d[12])                                     \
+                   : "n"(13 * (J - 1))                                                                                 \
+                   : __VA_ARGS__);                                                                                     \
+    break;
+    SIP_PARK_BANKS(SIP_PARK_READ)
+#undef SIP_PARK_READ
+  default:
+    break;
+  }
+  r.q0 = park_u4{d[0], d[1], d[2], d[3]};
+  r.q1 = park_u4{d[4], d[5], d[6], d[7]};
+  r.q2 = park_u4{d[8], d[9], d[10], d[11]};
+  r.tail = d[12];
+}
 
 // Fused factor + solve.  STAGED: stage blocks travel HBM -> LDS by LDS-DMA one
 // stage ahead of the arithmetic (needs N and M even: 16-byte pieces);
@@ -465,12 +578,17 @@ struct StagedCfg {
 // SPLIT (staged, mode 0 only): stage i's A | B of problem p are the N * (N + M) scalars at
 // ab + p * ab_pstride + i * ab_sstride (column-major A then B, as in the packed layout) and the
 // mats stage block is [Q | delta | M | R].
-template <int N, int M, bool STAGED, bool WPACK, bool SPLIT = false, bool SYM = false>
+// PARK (staged, packed spill, mode 0 only; the launcher sends the other modes to the plain kernel): the spill slots
+// of nodes 1 .. min(KEEP, T) stay on chip.  The backward sweep assembles each of them in an LDS image laid out as
+// the rollout's FW image and moves it, lane-linear, into a bank of accumulation registers; the rollout moves the
+// bank back into its stage buffer in place of the FW stream.  Slot 0 (read by the root) and the slots past KEEP
+// travel through `wsp` as before, so `wsp` holds no complete factor state after such a launch.
+template <int N, int M, bool STAGED, bool WPACK, bool SPLIT = false, bool SYM = false, bool PARK = false>
 __global__ __launch_bounds__(64) void chain_factor_solve_qw16(
     const double *__restrict__ mats, const double *__restrict__ vecs,
     double *__restrict__ sol, double *__restrict__ gains,
     double *__restrict__ wsp, int *__restrict__ status, const long batch,
-    const int T, const int mode, double *__restrict__ gfac,
+    const int T, const int mode_arg, double *__restrict__ gfac,
     const double *__restrict__ ab, const long ab_pstride, const long ab_sstride SIP_STAMP_ARG) {
   // mode 0: fused factor + solve.  mode 1 (split sip_lqr_factor): the backward sweep only, and the
   // LDL factors of the G matrices go to `gfac` ([problem][stage][Lt (M x M, column per lane) | 1/d
@@ -502,6 +620,10 @@ __global__ __launch_bounds__(64) void chain_factor_solve_qw16(
   constexpr int VSTG = L::VNODE + L::VEDGE; // vecs / sol stage stride
   constexpr int WSN = C::WSN;
   constexpr int WG = WPACK ? N * (N + 1) / 2 : N * N; // offset of g in a slot
+  static_assert(!PARK || (STAGED && C::PARK_OK), "PARK: a staged kernel with the packed spill, three rollout buffers and a 13-dword image");
+  const int mode = PARK ? 0 : mode_arg;
+  constexpr int KEEP = PARK ? C::KEEP : 0;
+  const int keep_e = KEEP < T ? KEEP : T; // nodes 1 .. keep_e are parked
 
   extern __shared__ double lds_raw[];
   lds_char *const lds = (lds_char *)lds_raw;
@@ -576,6 +698,23 @@ __global__ __launch_bounds__(64) void chain_factor_solve_qw16(
     if (lane < N)
       ((lds_double *)zeros)[lane] = 0.0;
   }
+  // PARK: the backward sweep's spill image (rows as in the FW image: row rr at rr * WSN * 8, the slot's own packed
+  // offsets) and, behind it, one dump slot per lane that takes the writes a lane does not own.
+  lds_char *const park_img = lds + C::PARK_AT;
+  lds_double *const park_row = (lds_double *)(park_img + rr * (WSN * 8));
+  // image -> registers of this lane, lane-linear as the LDS-DMA would land it
+  auto park_image_read = [&](lds_char *img, ParkRegs &r) {
+    typedef __attribute__((address_space(3))) park_u4 lds_u4;
+    lds_u4 *const q = (lds_u4 *)(img + lane * 16);
+    r.q0 = q[0], r.q1 = q[64], r.q2 = q[128];
+    r.tail = *(__attribute__((address_space(3))) unsigned *)(img + 3 * 1024 + lane * 4);
+  };
+  auto park_image_write = [&](lds_char *img, const ParkRegs &r) {
+    typedef __attribute__((address_space(3))) park_u4 lds_u4;
+    lds_u4 *const q = (lds_u4 *)(img + lane * 16);
+    q[0] = r.q0, q[64] = r.q1, q[128] = r.q2;
+    *(__attribute__((address_space(3))) unsigned *)(img + 3 * 1024 + lane * 4) = r.tail;
+  };
 
   // Loads [Q_i | q_i] as the augmented column.  nm / nv: stage block of mats /
   // vecs (global or LDS).
@@ -682,6 +821,22 @@ __global__ __launch_bounds__(64) void chain_factor_solve_qw16(
       if (valid)
         pw[(long)i * WSN + WG + N + c] = sum4(acc);
     }
+    if constexpr (PARK) {
+      if (i >= 1 && i <= keep_e) {
+        // A parked node: S and h go to the image (g follows from backward_edge(i - 1), which then parks the slot)
+        // and no vector-memory operation is issued.  Every row writes, the clamped ones of a short last wavefront
+        // included: they hold the last problem's values, which is what the FW stream would land there.
+        const int sbase = isM ? (c * N - (c * (c - 1)) / 2 - c) : 0;
+        const int dump = (C::PARK_SPAN + lane * 8 - rr * (WSN * 8)) / 8; // relative to park_row
+        sfor<0, N>([&](auto ii) {
+          constexpr int r = decltype(ii)::value;
+          park_row[(isM && r >= c) ? sbase + r : dump] = X[r];
+        });
+        if (isV)
+          sfor<0, N>([&](auto ii) { park_row[WG + N + decltype(ii)::value] = X[decltype(ii)::value]; });
+        return;
+      }
+    }
     if (valid && isV) { // h = S D^{-1/2} (c - delta o v)
       double *hn = pw + (long)i * WSN + WG + N;
       sfor<0, N>([&](auto ii) { hn[decltype(ii)::value] = X[decltype(ii)::value]; });
@@ -758,7 +913,22 @@ __global__ __launch_bounds__(64) void chain_factor_solve_qw16(
       });
     }
     rank1x<N, N, true>(F, W, Aaug);
-    if (valid && isV) {
+    bool g_parked = false;
+    if constexpr (PARK) {
+      if (i < keep_e) {
+        // g completes the image of node i + 1 (S and h are finish_node(i + 1)'s): park it.  The wavefront's LDS
+        // operations execute in order, so the lane-linear read sees every row's writes.
+        if (isV)
+          sfor<0, N>([&](auto ii) { park_row[WG + decltype(ii)::value] = F[decltype(ii)::value]; });
+        asm volatile("" ::: "memory");
+        ParkRegs pr;
+        park_image_read(park_img, pr);
+        park_bank<KEEP>(i + 1, pr);
+        asm volatile("" ::: "memory"); // finish_node(i) writes the image again
+        g_parked = true;
+      }
+    }
+    if (!g_parked && valid && isV) {
       double *gn = pw + (long)(i + 1) * WSN + WG;
       sfor<0, N>(
           [&](auto ii) { gn[decltype(ii)::value] = F[decltype(ii)::value]; });
@@ -915,7 +1085,14 @@ __global__ __launch_bounds__(64) void chain_factor_solve_qw16(
       // last vector-memory operations of the previous node (every lane issues
       // them, out-of-range ones included), so they may stay in flight:
       // everything older -- this stage's LDS-DMA -- is complete.
-      if constexpr (WPACK)
+      // PARK: node i + 1 <= keep_e issued no spill store at all.  What is younger than this stage's LDS-DMA is then
+      // the gain stores of edge i + 1 -- and how many instructions the compiler makes of those M doubles per lane
+      // is not the source's to say (it pairs them into 16-byte stores; a vmcnt(M) here left two instructions of the
+      // DMA in flight, which showed at batch 4096 only).  They were issued a node factorisation ago, so the wait
+      // for everything costs nothing.  The branch is wave-uniform.
+      if (PARK && i < keep_e)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      else if constexpr (WPACK)
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
       else
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1086,13 +1263,16 @@ __global__ __launch_bounds__(64) void chain_factor_solve_qw16(
     dma_fw.init(lane, (unsigned)(ws_len * 8), max_rel);
     dma_fd.init(lane, (unsigned)(mats_len * 8), max_rel);
   }
-  auto issue_forward = [&](const int i, lds_char *buf) {
+  // with_fw: the stage's spill slot streams from `wsp` (false under PARK for stages i < keep_e, whose slot of node
+  // i + 1 comes out of its register bank)
+  auto issue_forward = [&](const int i, lds_char *buf, const bool with_fw = true) __attribute__((always_inline)) {
     dma_fa.template issue<SIP_LQR_NT_FAB>(
         (const char *)(SPLIT ? ab + p0 * ab_pstride + (long)i * ab_sstride : mats + p0 * mats_len + (long)i * STG + L::NODE),
         buf, lane);
     dma_fg.template issue<SIP_LQR_NT_FSP>((const char *)(gains + p0 * gains_len + (long)i * L::GAIN),
                  buf + C::FA::BYTES, lane);
-    dma_fw.template issue<SIP_LQR_NT_FSP>((const char *)(wsp + p0 * ws_len + (long)(i + 1) * WSN),
+    if (with_fw)
+      dma_fw.template issue<SIP_LQR_NT_FSP>((const char *)(wsp + p0 * ws_len + (long)(i + 1) * WSN),
                  buf + C::FA::BYTES + C::FG::BYTES, lane);
     dma_fd.template issue<SIP_LQR_NT_FAB>(
         (const char *)(mats + p0 * mats_len + (long)(i + 1) * STG + L::QLEN),
@@ -1100,9 +1280,9 @@ __global__ __launch_bounds__(64) void chain_factor_solve_qw16(
   };
   if constexpr (STAGED) {
     if (T > 0)
-      issue_forward(0, lds);
+      issue_forward(0, lds, !PARK || 0 >= keep_e);
     if (C::F_NBUF == 3 && T > 1)
-      issue_forward(1, lds + C::F_BYTES);
+      issue_forward(1, lds + C::F_BYTES, !PARK || 1 >= keep_e);
   }
 
   // root (lqr.cpp:798-819): x_0 = -(I + Delta V)^{-1}(delta o v - c) = D^{1/2} h_0,
@@ -1122,7 +1302,25 @@ __global__ __launch_bounds__(64) void chain_factor_solve_qw16(
   int woff[N];
   spill_row_offsets(woff);
   int fbuf = 0; // LDS buffer of stage i = i % F_NBUF
-  for (int i = 0; i < T; ++i) {
+  // One stage of the rollout.  The flags are compile-time constants, so that every counted wait is an immediate that
+  // matches the LDS-DMA group in front of it on every path (tools/check_dpp_hazards.py follows the paths):
+  //   UNPARK:  i < keep_e      -- the spill slot of node i + 1 comes out of its register bank, not out of a stream;
+  //   SHORT:   i + 1 < keep_e  -- the look-ahead group in flight (stage i + 1) has no FW instructions;
+  //   FW_NEXT: i + 2 >= keep_e -- the group issued behind this stage (stage i + 2) has them;
+  //   AHEAD:   what is known of the stages behind this one where the regimes meet: ROLL_ASK asks (i + 1 < T for the
+  //            whole-group wait, i + 2 < T for the issue), ROLL_MORE: stage keep_e exists (the wait is counted, and at
+  //            i = keep_e - 2 the issue is unconditional), ROLL_LAST: it does not (keep_e = T: neither).
+  // Without PARK the flags are (false, false, true, ROLL_ASK) throughout.
+  constexpr int ROLL_ASK = 0, ROLL_MORE = 1, ROLL_LAST = 2;
+  auto roll_stage = [&](const int i, auto unpark_c, auto short_c, auto fw_next_c, auto ahead_c) __attribute__((always_inline)) {
+    constexpr bool UNPARK = decltype(unpark_c)::value, SHORT = decltype(short_c)::value,
+                   FW_NEXT = decltype(fw_next_c)::value;
+    constexpr int AHEAD = decltype(ahead_c)::value;
+    static_assert(PARK || AHEAD == ROLL_ASK, "");
+    constexpr int F_GLDS_SHORT = C::F_GLDS - C::FW::INSTR;
+    static_assert(F_GLDS_SHORT == C::FA::INSTR + C::FG::INSTR + C::FC::INSTR && F_GLDS_SHORT > 0, "");
+    static_assert(PARK || (!UNPARK && !SHORT && FW_NEXT), "");
+    static_assert(!SHORT || UNPARK, "stage i + 1 is parked only where stage i is");
     double KT[N], Arow[N], Brow[M], Wc[N];
     double kk0, gg, hh, dd;
     auto read_stage = [&](auto em, auto gi, auto wn, auto dp) {
@@ -1152,7 +1350,9 @@ __global__ __launch_bounds__(64) void chain_factor_solve_qw16(
       // operations of this wave: issued after the previous iteration's
       // stores) may stay in flight; everything older -- stage i -- has landed.
       static_assert(C::F_GLDS < 64, "vmcnt is 6 bits");
-      if (C::F_NBUF == 3 && i + 1 < T)
+      if constexpr (SHORT) // (i + 1 < keep_e <= T)
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(F_GLDS_SHORT) : "memory");
+      else if (C::F_NBUF == 3 && AHEAD != ROLL_LAST && (AHEAD == ROLL_MORE || i + 1 < T))
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::F_GLDS) : "memory");
       else
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1160,6 +1360,12 @@ __global__ __launch_bounds__(64) void chain_factor_solve_qw16(
       acc_fwait += ts_b - ts_a;
       lds_char *b1 = buf + C::FA::BYTES, *b2 = b1 + C::FG::BYTES,
                *b3 = b2 + C::FW::BYTES;
+      if constexpr (UNPARK) { // node i + 1 out of its bank, where the FW stream would have landed it
+        ParkRegs pr;
+        unpark_bank<KEEP>(i + 1, pr);
+        park_image_write(b2, pr);
+        asm volatile("" ::: "memory");
+      }
       read_stage((lds_cdouble *)(buf + rr * C::FA::ROW_BYTES),
                  (lds_cdouble *)(b1 + rr * C::FG::ROW_BYTES),
                  (lds_cdouble *)(b2 + rr * (WSN * 8)),
@@ -1212,10 +1418,46 @@ __global__ __launch_bounds__(64) void chain_factor_solve_qw16(
       // Keep the stores above older than the DMA below (see the vmcnt count).
       asm volatile("" ::: "memory");
       const int nbuf = fbuf >= 1 ? fbuf - 1 : C::F_NBUF - 1; // (i + 2) % 3
-      if (C::F_NBUF == 3 && i + 2 < T)
-        issue_forward(i + 2, lds + nbuf * C::F_BYTES);
+      // (a SHORT stage that is not the last regime's has stage i + 2 <= keep_e behind it)
+      if (C::F_NBUF == 3 && AHEAD != ROLL_LAST && ((AHEAD == ROLL_MORE && SHORT) || i + 2 < T))
+        issue_forward(i + 2, lds + nbuf * C::F_BYTES, FW_NEXT);
       fbuf = fbuf + 1 == C::F_NBUF ? 0 : fbuf + 1;
     }
+  };
+  using std::false_type;
+  using std::true_type;
+  using ask_t = std::integral_constant<int, ROLL_ASK>;
+  using more_t = std::integral_constant<int, ROLL_MORE>;
+  using last_t = std::integral_constant<int, ROLL_LAST>;
+  if constexpr (PARK) {
+    // Stages 0 .. keep_e - 1 read parked slots.  The regimes differ in the LDS-DMA groups around them, and each is
+    // a body of its own under ONE branch on whether stage keep_e exists, so that no path leads from a short group
+    // to a wait that counts a whole one.
+    int i = 0;
+    auto parked_head = [&]() __attribute__((always_inline)) { // i <= keep_e - 3: short groups before and behind
+      for (; i + 2 < keep_e; ++i)
+        roll_stage(i, true_type{}, true_type{}, false_type{}, more_t{});
+    };
+    if (keep_e < T) {
+      if (keep_e >= 2) {
+        parked_head();
+        roll_stage(i++, true_type{}, true_type{}, true_type{}, more_t{}); // i = keep_e - 2: stage keep_e streams its slot
+      }
+      if (keep_e >= 1)
+        roll_stage(i++, true_type{}, false_type{}, true_type{}, more_t{}); // i = keep_e - 1: a whole group in flight
+      for (; i < T; ++i)
+        roll_stage(i, false_type{}, false_type{}, true_type{}, ask_t{});
+    } else { // keep_e = T: parked to the end, nothing to issue behind the last two stages
+      if (keep_e >= 2) {
+        parked_head();
+        roll_stage(i++, true_type{}, true_type{}, true_type{}, last_t{});
+      }
+      if (keep_e >= 1)
+        roll_stage(i++, true_type{}, false_type{}, true_type{}, last_t{});
+    }
+  } else {
+    for (int i = 0; i < T; ++i)
+      roll_stage(i, false_type{}, false_type{}, true_type{}, ask_t{});
   }
 #ifdef SIP_LQR_STAMPS
   SIP_STAMP(ts_end);

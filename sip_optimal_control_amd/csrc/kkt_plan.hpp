@@ -420,6 +420,11 @@ inline std::string plan_name(const sip_kkt_plan &p) {
   std::string name = p.chain        ? std::string("chain:") + sip_lqr_kernel_name(p.chain)
                      : p.tree_fused ? std::string("tree:fused ") + sip_lqr_tree_split_kernel_name(p.tree)
                                     : std::string("tree:general");
+  // (the split form of a chain kernel is the plain kernel's: what the fused sweep of sip_lqr_factor_solve parks in
+  // registers -- the ",park" at the end of its name -- says nothing about a step that runs the split form)
+  const std::string park = ",park";
+  if (p.chain && p.chain_split && name.size() >= park.size() && name.compare(name.size() - park.size(), park.size(), park) == 0)
+    name.erase(name.size() - park.size());
   name += p.chain_kernels ? " + chain condensation" : p.staged ? " + staged condensation" : " + direct condensation";
   if (p.chain_split)
     name += p.chain_sym != nullptr ? " (A|B in place, Q|R packed)" : " (A|B in place)";

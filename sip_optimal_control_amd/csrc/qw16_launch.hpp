@@ -25,7 +25,10 @@ hipError_t launch_mrhs_qw16(long batch, int T, const void *mats, const void *vec
   return hipGetLastError();
 }
 
-template <int N, int M, bool STAGED, bool WPACK, bool SYM = false>
+// PARK: the fused sweep (mode 0) runs on the kernel that keeps the spill of its first KEEP nodes in accumulation
+// registers (chain_qw16.hpp); the factor and solve sweeps, whose spill IS the factor state later launches read, run on
+// the plain kernel of the shape.
+template <int N, int M, bool STAGED, bool WPACK, bool SYM = false, bool PARK = false>
 hipError_t launch_qw16(long batch, int T, const void *mats, const void *vecs, void *sol, void *gains,
                        int32_t *status, void *ws, hipStream_t stream, int mode, void *gfac) {
   using Cfg = StagedCfg<N, M, WPACK, false, SYM>;
@@ -37,10 +40,24 @@ hipError_t launch_qw16(long batch, int T, const void *mats, const void *vecs, vo
     if (bits & 15)
       return hipErrorInvalidValue;
   }
-  hipLaunchKernelGGL((chain_factor_solve_qw16<N, M, STAGED, WPACK, false, SYM>), dim3(blocks), dim3(64), lds, stream,
-                     (const double *)mats, (const double *)vecs, (double *)sol, (double *)gains, (double *)ws,
-                     (int *)status, batch, T, mode, (double *)gfac, (const double *)nullptr, 0L, 0L SIP_STAMP_PASS);
+  if (PARK && mode == 0)
+    hipLaunchKernelGGL((chain_factor_solve_qw16<N, M, STAGED, WPACK, false, SYM, PARK>), dim3(blocks), dim3(64), lds,
+                       stream, (const double *)mats, (const double *)vecs, (double *)sol, (double *)gains, (double *)ws,
+                       (int *)status, batch, T, mode, (double *)gfac, (const double *)nullptr, 0L, 0L SIP_STAMP_PASS);
+  else
+    hipLaunchKernelGGL((chain_factor_solve_qw16<N, M, STAGED, WPACK, false, SYM>), dim3(blocks), dim3(64), lds, stream,
+                       (const double *)mats, (const double *)vecs, (double *)sol, (double *)gains, (double *)ws,
+                       (int *)status, batch, T, mode, (double *)gfac, (const double *)nullptr, 0L, 0L SIP_STAMP_PASS);
   return hipGetLastError();
+}
+
+// KernelEntry::launch_park of an entry: the parked fused sweep where the manifest lists the shape, else none.
+template <int N, int M, bool STAGED, bool SYM>
+constexpr launch_fs_t park_launcher() {
+  if constexpr (STAGED && QW16_PARKED(N, M))
+    return &launch_qw16<N, M, STAGED, STAGED, SYM, true>;
+  else
+    return nullptr;
 }
 
 // The split form of the fused sweep (launch_split_t): A | B stream from where the model callback left them.
@@ -72,8 +89,11 @@ hipError_t launch_qw16_split(long batch, int T, const void *mats, const void *ab
 #define QW16_NONE(...) nullptr
 #define QW16_MRHS(N, M, STAGED, SYM) &sipamd::launch_mrhs_qw16<N, M, STAGED>
 #define QW16_SPLIT(N, M, STAGED, SYM) &sipamd::launch_qw16_split<N, M, SYM>
+// A staged entry of a shape the manifest lists as parked (QW16_PARKED) carries a second launcher, launch_park: the
+// fused sweep that parks its first spill slots in registers.  The factor and solve sweeps, the column sweep and the
+// split form of the entry stay the plain kernel's.
 #define QW16_ENTRY(N, M, STAGED, SYM, TAG, CORE, MRHS, SPLIT)                                                  \
-  { SIP_LQR_F64, N, M, "chain_factor_solve_qw16<" #N "," #M "," TAG ">/f64",                                   \
+  sipamd::with_park({ SIP_LQR_F64, N, M, "chain_factor_solve_qw16<" #N "," #M "," TAG ">/f64",                 \
     sipamd::StagedCfg<N, M, STAGED, false, SYM>::WSN, &sipamd::launch_qw16<N, M, STAGED, STAGED, SYM>,         \
     SYM ? SIP_LQR_LAYOUT_SYMMETRIC : SIP_LQR_LAYOUT_FULL, CORE, STAGED, /*solve_only*/ true,                   \
-    MRHS(N, M, STAGED, SYM), SPLIT(N, M, STAGED, SYM) }
+    MRHS(N, M, STAGED, SYM), SPLIT(N, M, STAGED, SYM) }, sipamd::park_launcher<N, M, STAGED, SYM>())

@@ -68,7 +68,15 @@ struct KernelEntry {
   const char *separate_suffix = "";      // what the opt-in appends to the plan's kernel name
   int sweep_columns = 0;                 // columns one launch of launch_solve_sweep carries
   int sweep_col_scalars = 0;             // scalars of column workspace per node and column
+  // the fp64 fused kernels: the fused sweep (mode 0 only) on the kernel that keeps its first spill slots in registers
+  // (chain_qw16.hpp, PARK); nullptr: the shape has none.  A plan of the shape itself runs sip_lqr_factor_solve on it
+  // unless SIP_LQR_PARK=0 at its creation; embedded shapes and every other sweep stay on launch_fs.
+  launch_fs_t launch_park = nullptr;
 };
+constexpr KernelEntry with_park(KernelEntry k, launch_fs_t launch_park) {
+  k.launch_park = launch_park;
+  return k;
+}
 // The separate sweeps of a row, and how its solve sweep carries columns.
 struct SeparateSweeps {
   launch_factor_sweep_t factor;

@@ -72,6 +72,11 @@ struct sip_lqr_plan {
   // sip_lqr_plan_set_wide_controls on a FULL-layout plan of the general engine with 9 <= m <= 16, n <= 32: the plan
   // runs on a row of kWideRows, its own (n = 32, m in {12, 16}) or, in fp64, embedded in the one with the least M >= m
   bool wide_controls = false;
+  // sip_lqr_factor_solve runs on the row's launch_park: the fused sweep that keeps the spill slots of its first nodes
+  // in accumulation registers (chain_qw16.hpp, PARK), so that the workspace holds no complete factor state after it.
+  // The plan's own shape only (not through the embedding), unless SIP_LQR_PARK=0 at creation; sip_lqr_kernel_name
+  // then ends in ",park".  Every other sweep of the plan is the row's launch_fs, launch_mrhs or launch_split.
+  bool park = false;
   std::string name_storage;
   Workspace ws;
 
@@ -137,7 +142,24 @@ struct DispatchEnv {
   bool core_only;       // SIP_LQR_EXTRA=0 (tests of the embedding): hides the slice entries outside the core set
   bool pad;             // SIP_LQR_PAD=0 clears it: no embedding
   bool split_general;   // SIP_LQR_SPLIT=general: split factor / solve stay on the general engine
+  int park;             // SIP_LQR_PARK (A/B timing, the bitwise test), where the plan's row has a parked fused sweep
+                        // (KernelEntry::launch_park): 0 keeps the plain kernel, 1 takes the parked one at any batch;
+                        // unset (-1): the parked one from park_min_batch() of the plan's device on
 };
+// The parked sweep trades HBM bytes for instructions on the wavefront's critical path: it wins where the launch is
+// bound by the memory side (batch 4096, four wavefronts per CU: -5 %) and loses where one wavefront per CU runs at its
+// own latency (batch 1024: +5 %).  In between the two layouts go either way by 1-3 %, so the
+// default parks where the win is measured: from four wavefronts per CU on -- LDS holds no more, so from there on
+// every SIMD of the chip runs one -- at four problems per wavefront: 16 problems per CU, batch 4096 on the 256 CUs
+// of an MI355X.  A plan without a device (host-side entry points only) does not park.
+int64_t park_min_batch(int device) {
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) {
+    (void)hipGetLastError();
+    return INT64_MAX;
+  }
+  return 16 * (int64_t)cus;
+}
 DispatchEnv dispatch_env() {
   auto is = [](const char *key, const char *value) {
     const char *v = std::getenv(key);
@@ -147,7 +169,7 @@ DispatchEnv dispatch_env() {
   if (variant != nullptr && variant[0] == 0)
     variant = nullptr;
   return {variant, is("SIP_LQR_VARIANT", "general"), extra != nullptr && extra[0] == '0', !is("SIP_LQR_PAD", "0"),
-          is("SIP_LQR_SPLIT", "general")};
+          is("SIP_LQR_SPLIT", "general"), is("SIP_LQR_PARK", "0") ? 0 : is("SIP_LQR_PARK", "1") ? 1 : -1};
 }
 
 // kKernels, then the fused fp64 kernels of every shape n <= 16, m <= 8 (the slices of qw16_kernels.hip, where
@@ -241,9 +263,13 @@ void decide_kernel(sip_lqr_plan *p, const KernelEntry *k, bool embedded, const D
   p->kernel = k;
   p->padded = embedded;
   p->dims = sipamd::embed::pad_dims(p->n, p->m, embedded ? k->n : p->n, embedded ? k->m : p->m, p->T);
+  p->park = k != nullptr && !embedded && k->launch_park != nullptr &&
+            (env.park == 1 || (env.park < 0 && p->batch >= park_min_batch(p->device)));
   if (embedded)
     p->name_storage = std::string(k->name) + " embedding (" + std::to_string(p->n) + "," + std::to_string(p->m) + ")";
-  p->kernel_name = embedded ? p->name_storage.c_str()
+  else if (p->park)
+    p->name_storage = std::string(k->name) + ",park";
+  p->kernel_name = embedded || p->park ? p->name_storage.c_str()
                    : k      ? k->name
                             : (p->dtype == SIP_LQR_F32 ? "tree_generic(chain layout)/f32"
                                                        : "tree_generic(chain layout)/f64");
@@ -328,6 +354,7 @@ hipError_t run_fused(const sip_lqr_plan *p, const void *mats, const void *vecs, 
   if (e == hipSuccess)
     e = factor_sweep  ? k.launch_factor_sweep(B, p->T, km, kgains, status, ws, w + f.gfac, s)
         : solve_sweep ? k.launch_solve_sweep(B, p->T, km, kv, ksol, kgains, ws, w + f.gfac, nullptr, status, 1, 0L, s)
+        : p->park && mode == Sweep::Full ? k.launch_park(B, p->T, km, kv, ksol, kgains, status, ws, s, 0, w + f.gfac)
                       : k.launch_fs(B, p->T, km, kv, ksol, kgains, status, ws, s, (int)mode, w + f.gfac);
   if (e == hipSuccess && p->padded)
     sipamd::embed::extract_outputs(p->dims, B, w + f.sol, sol, solve_sweep ? status : nullptr, w + f.pgains, gains, s);
